@@ -1,8 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- rollouts/sec per `.command()` call (BASELINE.json metric) on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c4] [--rng philox|philox7|philox-stream|philox-fused|torch-native|torch]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR] [--workload c3|c2|c4]
+                    [--rng philox|philox7|philox-stream|philox-fused|torch-native|torch]
 
+A plain run does what the headline figure needs and no more: set-up (the controller, and a probe controller that measures
+lambda and then carries the clock warm-up), W warm-up commands, K timed commands, the JSON line (metric, value, unit,
+ms_per_step, config).  Everything else this text describes -- the roofline objects and their extra passes, `latency_ms_synced`,
+the other noise modes, workloads, sizes and controllers, weak scaling for N > 1, `cpu_baseline`, the lookups -- is measured and
+printed with `--full` only.  `--dump-outputs DIR` writes what the last timed command returned and left (action.npy, U.npy,
+cost_total.npy; float32): the timed controller has issued exactly W + K commands by then, on a seeded problem, so two runs with
+the same arguments start from the same inputs and write the same arrays.
 A "step" is one full `MPPI.command(state)`: on-device noise draw, fused rollout+cost (K1),
 exp-weighting + weighted update (K3/K4) and, for N>1, the single record all-gather + combine.
 Default noise mode: rng="philox" -- the engine's own Philox4x32-10 + Box-Muller generator on the
@@ -210,6 +218,16 @@ def clock_warmup(ctrl, x0, seconds=CLOCK_WARMUP_S):
         n += 10
         torch.cuda.synchronize()
     return n
+
+
+def dump_outputs(directory, **arrays):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the action the last `command()` returned,
+    the nominal sequence it left (`get_action_sequence()`) and the K rollout costs (`cost_total`; rank 0's shard when sharded)
+    -- as <directory>/<name>.npy, float32 (4 * (nu + T * nu + K) bytes: 0.3 MB at the default workload)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def _stats(xs):
@@ -567,10 +585,29 @@ def main_devices(args, choice=None):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ctrl.command(x0)
+        action = ctrl.command(x0)
     t_issue = time.perf_counter() - t0
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, action=action, U=ctrl.shards[0].U)
+    out = {
+        "metric": "rollouts/sec (K x T state evals) per .command() call",
+        "value": Kglobal * args.steps / dt, "unit": "rollouts/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": desc, "K_per_gpu": Kper, "K_global": Kglobal, "T": T, "nx": nx, "nu": nu, "rng": args.rng,
+                   "draw": ctrl.last_draw or "torch.randn", "lambda": float(ctrl.lambda_), "sharding": f"samples/{n}",
+                   "devices": devs,
+                   "process_model": "ONE process, MPPI(..., devices=[...]) (pytorch_mppi_amd/group.py): " + ctrl.exchange + "; launches issued by "
+                                    + ctrl.issue + ("" if have >= n else f" -- {n} shards share {have} GPU(s): exercises the code path, not a measurement")},
+        "state_evals_per_s": Kglobal * T * args.steps / dt,
+    }
+    if not args.full:
+        if choice is not None:                      # --process-model auto: what decided, measured before this run
+            out["config"]["process_model_choice"] = choice
+        print(json.dumps(out), flush=True)
+        return
     identical = bool(all(torch.equal(ctrl.shards[0].U.cpu(), s_.U.cpu()) for s_ in ctrl.shards[1:]))
     one, x1, _ = make_controller(pm, args.workload, dev0, args.rng, None, Kper)
     one.lambda_ = float(ctrl.lambda_)
@@ -586,18 +623,8 @@ def main_devices(args, choice=None):
     if choice is None:
         choice = host_issue_probe(pm, args.workload, devs, args.rng)
         choice.update(host_issue_us_per_device=choice["caller_us"] / n, rule="--process-model devices (forced)")
-    out = {
-        "metric": "rollouts/sec (K x T state evals) per .command() call",
-        "value": Kglobal * args.steps / dt, "unit": "rollouts/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": desc, "K_per_gpu": Kper, "K_global": Kglobal, "T": T, "nx": nx, "nu": nu, "rng": args.rng,
-                   "draw": ctrl.last_draw or "torch.randn", "lambda": float(ctrl.lambda_), "sharding": f"samples/{n}",
-                   "devices": devs, "devices_hold_identical_U": identical,
-                   "process_model": "ONE process, MPPI(..., devices=[...]) (pytorch_mppi_amd/group.py): " + ctrl.exchange + "; launches issued by "
-                                    + ctrl.issue + ("" if have >= n else f" -- {n} shards share {have} GPU(s): exercises the code path, not a measurement"),
-                   "process_model_choice": choice},
-        "state_evals_per_s": Kglobal * T * args.steps / dt,
+    out["config"].update(devices_hold_identical_U=identical, process_model_choice=choice)
+    out.update({
         "host_issue_us_per_command_in_the_timed_region": t_issue / args.steps * 1e6,
         "host_issue_us_per_device": choice.get("host_issue_us_per_device"),
         "roofline": None,
@@ -606,7 +633,7 @@ def main_devices(args, choice=None):
                          "note": "against the same workload unsharded at K_per_gpu on device 0, timed in this run with the same loop.  Each "
                                  "device's launches are issued by a worker thread of the engine (csrc/group.hip): the calling thread's share "
                                  "is the N problem blocks (`host_issue_us_per_device` x N; config.process_model_choice has the split)"},
-    }
+    })
     print(json.dumps(out), flush=True)
 
 
@@ -642,9 +669,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--rng", default="philox", choices=["torch", "torch-native", "philox", "philox7", "philox-stream", "philox-fused"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--hbm-cold", action="store_true", help="with --no-extras: still run the HBM-cold K1 pass (for a rocprofv3 trace of those launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the roofline passes (HIP-event clock, streaming form, HBM-cold K1), the synchronised "
+                         "latency, the other noise modes / workloads / sizes / controllers, weak scaling for N > 1 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed command returned and left (action, U, cost_total) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave the other modes / workloads / sizes out")
+    ap.add_argument("--hbm-cold", action="store_true", help="with --full --no-extras: still run the HBM-cold K1 pass (for a rocprofv3 trace of those launches)")
     ap.add_argument("--process-model", default="auto", choices=["auto", "devices", "spawn"],
                     help="--gpus N outside torch.distributed.run: 'devices' = ONE process, MPPI(..., devices=[0..N-1]); 'spawn' = start N ranks "
                          "(one process per GPU, shard=(rank, N)) like the driver's launcher does; 'auto' = whichever scales here: devices "
@@ -711,19 +743,15 @@ def main():
 
     # healthy softmax: lambda ~ std of the rollout cost, measured by a throw-away
     # probe controller (its first update, made at lambda=1, is an argmin copy and is discarded)
+    probe, _, _ = make_controller(pm, args.workload, device, args.rng, shard, Kglobal)
     if kind != "pendulum":
-        probe, _, _ = make_controller(pm, args.workload, device, args.rng, shard, Kglobal)
         probe.command(x0)
         lam = probe.cost_total.float().std()
         if world > 1:
             lam = lam.cpu() if backend != "nccl" else lam
             dist.all_reduce(lam, op=dist.ReduceOp.SUM)
             lam = lam / world
-        ctrl.lambda_ = float(lam)
-        del probe
-
-    # torch-generator modes: every rank draws its own shard, so the ranks need distinct streams
-    torch.manual_seed(1234 + rank)
+        ctrl.lambda_ = probe.lambda_ = float(lam)
 
     def barrier():
         if world > 1:
@@ -732,26 +760,33 @@ def main():
 
     from pytorch_mppi_amd import _native as N
     lib = N.lib()
-    for _ in range(args.warmup):
-        ctrl.command(x0)
     # (the timed region is `steps` commands -- 1.6 ms at the driver's 20: one collector pause inside it is 5-10 % of the figure.
     #  Collected and switched off HERE, in front of the clock warm-up: a collection takes milliseconds in which the GPU idles and
     #  clocks down -- put between the warm-up and the region it cost the on-chip K1 5 us per launch, 75.4 against 70.7)
     import gc
     gc.collect()
     gc.disable()
-    n_clock_warmup = clock_warmup(ctrl, x0)
+    # The clock warm-up lasts a TIME, so its number of commands differs from run to run: it runs on the probe (the same
+    # commands, the same kernels), and the timed controller has issued exactly --warmup + --steps commands when it stops --
+    # the same draws and the same nominal sequence in every run with the same arguments, which --dump-outputs relies on
+    n_clock_warmup = clock_warmup(probe, x0)
+    # torch-generator modes: every rank draws its own shard, so the ranks need distinct streams (seeded HERE: the probe drew
+    # from the same generator)
+    torch.manual_seed(1234 + rank)
+    for _ in range(args.warmup):
+        ctrl.command(x0)
     # device-clock stamps on every K1 launch of the timed region: no extra packets, no events (see the docstring)
     lib.mppi_profile_enable(STAMPS_ONLY)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ctrl.command(x0)
+        action = ctrl.command(x0)
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
     k1_dev_us, _ = N.profile_read_launches()
     lib.mppi_profile_enable(0)
+    del probe
     dump = os.environ.get("MPPI_BENCH_DUMP_LAUNCHES")
     if dump and rank == 0:
         # per-launch device-clock spans of the timed region, for tools/clock_calibration.py (matched against the
@@ -764,6 +799,29 @@ def main():
         tt = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
+    ms_per_step = dt / args.steps * 1e3
+    value = Kglobal * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, action=action, U=ctrl.U, cost_total=ctrl.cost_total)
+    out = {
+        "metric": "rollouts/sec (K x T state evals) per .command() call",
+        "value": value, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "clock_warmup_commands": n_clock_warmup,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": desc, "K_per_gpu": Kper, "K_global": Kglobal, "T": T, "nx": nx, "nu": nu,
+                   "rng": args.rng, "draw": ctrl.last_draw or "torch.randn", "lambda": float(ctrl.lambda_),
+                   "sharding": f"samples/{world}" if world > 1 else "none"},
+        "state_evals_per_s": value * T,
+    }
+    if not args.full:
+        # the plain run stops here: set-up, warm-up, the timed steps, the line
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     ranks_identical = None
     exchange = None
     if world > 1:
@@ -776,8 +834,6 @@ def main():
         allU = allU.view(world, -1)
         ranks_identical = bool(all(torch.equal(allU[0], allU[r]) for r in range(world)))
         exchange = exchange_time_us(ctrl, dist, barrier)
-    ms_per_step = dt / args.steps * 1e3
-    value = Kglobal * args.steps / dt
     n_eff = None
     if ctrl.omega is not None:
         s2 = (ctrl.omega.double() ** 2).sum()
@@ -950,19 +1006,8 @@ def main():
                 roofline.update({"frac_hbm_cold": ach_c / HBM_PEAK_GBS, "achieved_hbm_cold": ach_c,
                                  "median_launch_us_hbm_cold": us_c, "hbm_cold_sample": cold})
 
-    out = {
-        "metric": "rollouts/sec (K x T state evals) per .command() call",
-        "value": value, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "clock_warmup_commands": n_clock_warmup,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": desc, "K_per_gpu": Kper, "K_global": Kglobal, "T": T, "nx": nx, "nu": nu,
-                   "rng": args.rng, "draw": ctrl.last_draw or "torch.randn", "lambda": float(ctrl.lambda_), "n_eff": n_eff,
-                   "sharding": f"samples/{world}" if world > 1 else "none",
-                   "ranks_hold_identical_U": ranks_identical},
-        "state_evals_per_s": value * T,
-        "roofline": roofline,
-    }
+    out["config"].update(n_eff=n_eff, ranks_hold_identical_U=ranks_identical)
+    out["roofline"] = roofline
     if onchip is not None:
         # The headline's timed region runs rollout_onchip_kernel (+ finalize_blocks): `roofline` describes THAT kernel (VERDICT r04
         # item 1).  It reads no (K,T,nu) array, so it has no algorithmic HBM bytes to speak of and is bound by VALU issue (the

@@ -234,7 +234,7 @@ def test_two_processes_sharded_command_matches_unsharded():
 def test_bench_two_ranks_prints_one_valid_json_line():
     """bench.py under torch.distributed.run with 2 ranks (gloo test rig): weak scaling bookkeeping"""
     import json
-    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", "c2"],
+    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", "c2", "--full"],
                   env_extra={"MPPI_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -253,7 +253,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MPPI_BENCH_BACKEND")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--workload", "c2", "--process-model", "spawn"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--workload", "c2", "--process-model", "spawn", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -308,7 +308,7 @@ def test_bench_gpus_2_in_one_process_on_a_device_group():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MPPI_BENCH_BACKEND")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--process-model", "devices"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--process-model", "devices", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
