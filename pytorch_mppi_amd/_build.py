@@ -18,11 +18,15 @@ LIB = os.path.join(HERE, f"libmppi_amd{SUFFIX}.so")
 OBJ_DIR = os.path.join(CSRC, "build" + SUFFIX)
 SOURCES = ["capi.hip", "dist.hip", "group.hip", "update.hip", "rollout_pendulum.hip", "rollout_integrator.hip",
            "rollout_linear_goal.hip", "rollout_mlp.hip", "rollout_mlp_mfma.hip", "rollout_mlp_split.hip",
-                   "noise_torch.hip"]
+                   "rollout_mlp_split32.hip", "noise_torch.hip"]
 # translation units: (source, object name, extra flags).  The two heaviest sources are compiled as several units each
 # (groups of model dimensions selected with a define) so that the parallel build is not one long compile
 _GROUPS = {"rollout_integrator.hip": ("MPPI_INTEGRATOR_GROUP", 4), "rollout_linear_goal.hip": ("MPPI_LINEAR_GROUP", 3),
-           "rollout_mlp.hip": ("MPPI_MLP_GROUP", 6), "rollout_mlp_split.hip": ("MPPI_SPLIT_GROUP", 2)}
+           "rollout_mlp.hip": ("MPPI_MLP_GROUP", 8), "rollout_mlp_split.hip": ("MPPI_SPLIT_GROUP", 2)}
+# no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the units added since round 6: no faster than two scalar
+# instructions on gfx950 (see EXTRA), and the older units keep their flags, i.e. their code, as measured
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+_GROUP_FLAGS = {("rollout_mlp.hip", 6): NO_PK_F32, ("rollout_mlp.hip", 7): NO_PK_F32}
 
 
 def _units():
@@ -30,7 +34,7 @@ def _units():
     for src in SOURCES:
         if src in _GROUPS:
             for g in range(_GROUPS[src][1]):
-                units.append((src, src.replace(".hip", f"_g{g}.o"), [f"-D{_GROUPS[src][0]}={g}"]))
+                units.append((src, src.replace(".hip", f"_g{g}.o"), [f"-D{_GROUPS[src][0]}={g}"] + _GROUP_FLAGS.get((src, g), [])))
         else:
             units.append((src, src.replace(".hip", ".o"), []))
     # longest first (measured seconds per unit on the build container, 8 at a time): the pool starts the big ones first
@@ -41,7 +45,7 @@ def _units():
             "rollout_mlp_g2.o": 75, "rollout_pendulum.o": 70, "rollout_linear_goal_g1.o": 68,
                     "rollout_integrator_g3.o": 45,
             "rollout_mlp_g3.o": 75, "rollout_mlp_g4.o": 75, "rollout_mlp_g5.o": 75, "rollout_mlp_split_g0.o": 30,
-            "rollout_mlp_split_g1.o": 35}
+            "rollout_mlp_split_g1.o": 35, "rollout_mlp_g6.o": 90, "rollout_mlp_g7.o": 80, "rollout_mlp_split32.o": 45}
     return sorted(units, key=lambda u: -cost.get(u[1], 5))
 # -ffp-contract=fast: mul+add pairs fuse into v_fma / v_pk_fma.  torch eager rounds twice where
 # the kernels round once, a <= 1 ulp difference per operation that the parity tests bound
@@ -58,6 +62,8 @@ EXTRA = {"update.hip": ["-mllvm", "-pragma-unroll-threshold=200000"],
          # (-fno-slp-vectorize: the fp16 residual of the activation split is one v_fma_mix_f32 per value only when the
          # SLP vectorizer does not pair two of them into v_cvt_f32_f16 x 2 + v_pk_fma_f32 first)
          "rollout_mlp_split.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+         # its two-output-tile form (16 < nx <= 32): the same arithmetic, the same flags
+         "rollout_mlp_split32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] + NO_PK_F32,
          # the KMPPI-fused K1 (rollout_kmppi.hpp) pins 256 control points in the AGPRs and reads its 4 x nu
          # accumulator tile with the VALU: same flag for every unit that instantiates it (jit.py passes it too)
          "rollout_integrator.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

@@ -124,6 +124,12 @@ SYMBOLS = {
             C.POINTER(C.c_int64)]),
 }
 
+# exported by the library but not declared in include/mppi_amd.h yet (csrc/mlp_split32.hpp: they join the header, and
+# SYMBOLS, at the next ABI bump)
+EXTRA_SYMBOLS = {
+    "mppi_stat_mlp_split32_launches": (C.c_int64, []),
+}
+
 _lib = None
 
 
@@ -153,7 +159,7 @@ def lib():
         l = C.CDLL(path)
     except OSError as e:
         raise RuntimeError(f"pytorch_mppi_amd: cannot load {path}: {e}; there is no CPU fallback") from e
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **EXTRA_SYMBOLS}.items():
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

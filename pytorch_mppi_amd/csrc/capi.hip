@@ -9,6 +9,7 @@
 #include <cstring>
 #include <hip/hip_ext.h>
 #include "dispatch.hpp"
+#include "mlp_split32.hpp"   // mppi_stat_mlp_split32_launches: defined by rollout_mlp_split32.hip, part of this C-ABI
 #include "update.hpp"
 
 using namespace mppi;

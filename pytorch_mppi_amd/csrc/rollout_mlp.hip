@@ -2,6 +2,7 @@
 // BASELINE.json configs[3..4] are (nx,nu,H)=(16,4,256).
 #include <cstdlib>
 #include "dispatch.hpp"
+#include "mlp_split32.hpp"
 #include "rollout.hpp"
 namespace mppi {
 // One translation unit per (nx,nu) pair (MPPI_MLP_GROUP, set by _build.py; chained like rollout_integrator.hip): the per-lane
@@ -17,6 +18,9 @@ namespace mppi {
 #define MPPI_MLP_DIMS_3(X) X(8, 2)
 #define MPPI_MLP_DIMS_4(X) X(12, 6)
 #define MPPI_MLP_DIMS_5(X) X(16, 8)
+// ... and of its two-output-tile form (rollout_mlp_split32.hip: 16 < nx <= 32)
+#define MPPI_MLP_DIMS_6(X) X(32, 8)
+#define MPPI_MLP_DIMS_7(X) X(24, 6)
 #if MPPI_MLP_GROUP == 0
 #define MPPI_DIMS MPPI_MLP_DIMS_0
 #define MPPI_THIS rollout_mlp_valu
@@ -25,6 +29,7 @@ bool supported_mlp(int nx, int nu, int hidden) {
   if (hidden <= 0) return false;
 #define X(NX, NU) if (nx == NX && nu == NU) return true;
   MPPI_MLP_DIMS_0(X) MPPI_MLP_DIMS_1(X) MPPI_MLP_DIMS_2(X) MPPI_MLP_DIMS_3(X) MPPI_MLP_DIMS_4(X) MPPI_MLP_DIMS_5(X)
+  MPPI_MLP_DIMS_6(X) MPPI_MLP_DIMS_7(X)
 #undef X
   return false;
 }
@@ -44,17 +49,36 @@ bool supported_mlp(int nx, int nu, int hidden) {
 #define MPPI_DIMS MPPI_MLP_DIMS_4
 #define MPPI_THIS rollout_mlp_valu_g4
 #define MPPI_NEXT rollout_mlp_valu_g5
-#else
+#elif MPPI_MLP_GROUP == 5
 #define MPPI_DIMS MPPI_MLP_DIMS_5
 #define MPPI_THIS rollout_mlp_valu_g5
+#define MPPI_NEXT rollout_mlp_valu_g6
+#elif MPPI_MLP_GROUP == 6
+#define MPPI_DIMS MPPI_MLP_DIMS_6
+#define MPPI_THIS rollout_mlp_valu_g6
+#define MPPI_NEXT rollout_mlp_valu_g7
+#else
+#define MPPI_DIMS MPPI_MLP_DIMS_7
+#define MPPI_THIS rollout_mlp_valu_g7
 #endif
 #ifdef MPPI_NEXT
 int MPPI_NEXT(const KArgs<float>& a, hipStream_t st);
 int MPPI_NEXT(const KArgs<double>& a, hipStream_t st);
 #endif
+// More than 16 states: the per-lane kernels keep ONE rolled copy of the step (rollout.hpp model_heavy) and serve one state
+// rollout per action sequence -- the multi-rollout instantiations of these shapes spill vector registers (35 at (32, 8)), so
+// they are not built and M > 1 runs the callback loop (models.MLPResidual.heavy).
+template <typename T, int NX, int NU>
+struct MlpModelRolled : MlpModel<T, NX, NU> {
+  static constexpr bool HEAVY = true;
+  __device__ explicit MlpModelRolled(const KArgs<T>& a) : MlpModel<T, NX, NU>(a) {}
+};
+template <typename T, int NX, int NU>
+using MlpPerLane = std::conditional_t<(NX > 16), MlpModelRolled<T, NX, NU>, MlpModel<T, NX, NU>>;
+
 template <typename T> static int go(const KArgs<T>& a, hipStream_t st) {
   if (a.mp == nullptr || a.hidden <= 0) return MPPI_E_BADARG;
-#define X(NX, NU) if (a.nx == NX && a.nu == NU) return launch_rollout<MlpModel<T, NX, NU>, T>(a, st);
+#define X(NX, NU) if (a.nx == NX && a.nu == NU) return launch_rollout<MlpPerLane<T, NX, NU>, T>(a, st);
   MPPI_DIMS(X)
 #undef X
 #ifdef MPPI_NEXT
@@ -82,8 +106,15 @@ int rollout_mlp(const KArgs<float>& a, hipStream_t st) {
   const bool force_exact = (fe != nullptr && fe[0] == '1') || (a.model_flags & MPPI_MODEL_FLAG_EXACT_FP32) != 0;
   const bool smppi = a.B != nullptr || a.smooth_w != 0.f;      // lifted controls: the split kernel has the base sequence,
                                                                // the 1/dt rescaling and the smoothness cost; the exact one not
+  if (!force_valu && !force_exact && a.M == 1 && a.states == nullptr && mlp_split32_supported(a.nx, a.nu, a.hidden)) {
+    // 16 < nx <= 32: the two-output-tile split-operand kernel (rollout_mlp_split32.hip), same rules as below
+    if (a.noise_src == MPPI_NOISE_KTN) return MPPI_E_UNSUPPORTED;
+    const int r = rollout_mlp_split32(a, st);
+    if (r != MPPI_E_UNSUPPORTED) return r;
+    // (rows it does not read, or a horizon whose tables do not fit the LDS beside the layer-1 weights: per lane)
+  }
   if (!force_valu && a.M == 1 && a.states == nullptr) {
-    const bool use_split = !force_exact && mlp_split_supported(a.nx, a.nu, a.hidden);
+    const bool use_split =!force_exact && mlp_split_supported(a.nx, a.nu, a.hidden);
     const bool exact_ok = !smppi && mlp_mfma_supported(a.nx, a.nu, a.hidden);
     if (use_split || exact_ok) {
       // the matrix-core kernels read the engine's own layout: ask the caller to convert a (K,T,nu) draw

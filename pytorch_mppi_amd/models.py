@@ -159,8 +159,9 @@ class LinearGoal(NativeModel):
         return ((goal - states[..., -1, :]) ** 2).sum(dim=-1)
 
 
-# (nx, nu) with an instantiation of the split-operand matrix-core kernel (csrc/rollout_mlp_split.hip MPPI_SPLIT_DIMS_*)
-MLP_MATRIX_CORE_SHAPES = ((16, 4), (8, 2), (12, 6), (16, 8))
+# (nx, nu) with an instantiation of the split-operand matrix-core kernel (csrc/rollout_mlp_split.hip MPPI_SPLIT_DIMS_*; the
+# last two: its two-output-tile form for 16 < nx <= 32, csrc/rollout_mlp_split32.hip MPPI_SPLIT32_DIMS)
+MLP_MATRIX_CORE_SHAPES = ((16, 4), (8, 2), (12, 6), (16, 8), (32, 8), (24, 6))
 
 
 def mlp_kernel_width(nx, nu, hidden):
@@ -206,6 +207,9 @@ class MLPResidual(NativeModel):
         # built for (hidden 100 on the per-lane kernel costs 13 x the matrix-core time)
         self.hidden_units = int(self.W1.shape[0])
         self.hidden = mlp_kernel_width(nx, nu, self.hidden_units)
+        # more than 16 states: the per-lane kernels are built for one state rollout per action sequence only (their
+        # multi-rollout form spills registers, csrc/rollout_mlp.hip) -- rollout_samples > 1 runs the callback loop
+        self.heavy = self.nx > 16
         self.res_scale = float(res_scale)
         self.q_state = torch.ones(self.nx, dtype=torch.float64) if q_state is None else torch.as_tensor(q_state,
                 dtype=torch.float64).reshape(-1)
