@@ -128,6 +128,8 @@ SYMBOLS = {
 # SYMBOLS, at the next ABI bump)
 EXTRA_SYMBOLS = {
     "mppi_stat_mlp_split32_launches": (C.c_int64, []),
+    # (csrc/capi.hip: the two-wave on-chip kernel's split of a wave's rows -- registers / LDS / memory / resident / regenerated)
+    "mppi_onchip_pair_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -678,6 +678,17 @@ extern "C" int64_t mppi_onchip_spill_elems(const MppiProblem* p) {
   return n;
 }
 
+// Where the rows of the two-waves-per-sample kernel wait at this shape, as the next launch would split them (MPPI_PAIR_TAIL and
+// MPPI_PAIR_DLS as they are now): out = P4, SW, CH, KR, nch, nls, ntl, nsl, nsm, nres, nmem, nregen (csrc/common.hpp
+// OnChipPairGeometry).  Returns 1 when the form's tables fit, else 0.  (Not in include/mppi_amd.h yet: it joins at the next ABI bump.)
+extern "C" int mppi_onchip_pair_split(int nu, int nx, int T, int plain, int32_t* out) {
+  if (out == nullptr || nu <= 0 || nx <= 0 || T <= 0) return 0;
+  const mppi::OnChipPairGeometry g = mppi::onchip_pair_geometry(nu, nx, T, plain != 0, mppi::onchip_pair_tail());
+  const int v[12] = {g.P4, g.SW, g.CH, g.KR, g.nch, g.nls, g.ntl, g.nsl, g.nsm, g.nres, g.nmem, g.nregen};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
+  return g.ok ? 1 : 0;
+}
+
 extern "C" int mppi_command(const MppiProblem* p, int apply, void* stream) {
   t_next_draw = 0;
   // small problems: K1's launch carries K3 and K4 as well when the caller left omega and

@@ -134,11 +134,26 @@ static inline OnChipGeometry onchip_geometry(int nu, int Tn, bool diag) {
 #endif
 struct OnChipPairGeometry {
   int P4, TT, SW, CH, KR, nss, nch, nit, nls, ntl, nsl, nsm, shn;
+  // what the kernel does with the ntl * SW - KR - nsl local super-steps beyond registers and LDS: the first `nmem` wait in memory, the
+  // wave's last `nres` real ones stay resident in the registers of the last iteration, `nregen` -- the ones between, and the padding
+  // behind the last chunk -- are generated a second time (padding: nothing to generate).  KR + nsl + nmem + nregen + nres = ntl * SW.
+  // `nsm` sizes the caller's array (mppi_onchip_spill_elems) and keeps the value it had before there were resident rows: nmem <= nsm.
+  int nres, nmem, nregen;
   size_t smem;
   bool ok;
 };
+// MPPI_PAIR_TAIL: 1 (default) = the last chunk stays resident, 0 = it is generated a second time (the kernel as it was) -- like
+// MPPI_ONCHIP_PAIR read at every launch: an A/B switch that tests flip inside one process
+#ifndef MPPI_PAIR_TAIL_DEFAULT
+#define MPPI_PAIR_TAIL_DEFAULT 1
+#endif
+static inline int onchip_pair_tail() {
+  const char* e = getenv("MPPI_PAIR_TAIL");
+  return (e && *e) ? atoi(e) : MPPI_PAIR_TAIL_DEFAULT;
+}
 // plain: the command without |noise| cost, u_scale, SMPPI terms; otherwise the previous timestep's action rides in the hand-over too
-static inline OnChipPairGeometry onchip_pair_geometry(int nu, int nx, int Tn, bool plain = true) {
+// tail: onchip_pair_tail() for a launch; the array's size (nsm) does not depend on it
+static inline OnChipPairGeometry onchip_pair_geometry(int nu, int nx, int Tn, bool plain = true, int tail = 0) {
   OnChipPairGeometry g{};
   const int G = (nu % 4 == 0) ? 4 : ((nu % 2 == 0) ? 2 : 1);
   g.P4 = nu / G;
@@ -163,14 +178,15 @@ static inline OnChipPairGeometry onchip_pair_geometry(int nu, int nx, int Tn, bo
   if (nsl > room) nsl = (int)room;
   nsl -= nsl % g.SW;
   g.nsl = nsl;
-  // The wave's last `dls` local super-steps are generated a second time instead of waiting in memory: the weighting phase is bound
-  // either by the fetch of the memory rows (out of the Infinity Cache, chip-wide) or by its VALU work (column sums + second generation,
-  // two waves per SIMD), and the two proceed side by side.  Measured at C3 (profiles/r06_k_onchip_pair_check.txt; 22 real super-steps
-  // beyond registers and LDS, 3 of padding): dls = 0 / 5 / 10 / 15 -> 67.1 / 62.0 / 60.4 / 62.9 us, splits inside a tile (6, 7: 62.3,
-  // 62.4) no better than their neighbours -- so whole tiles, as many as bring the regenerated share closest to a third of the real
-  // super-steps out there (C3: the last two tiles = 7 of 22).  MPPI_PAIR_DLS in the environment overrides it (measurements; any value).
+  // THE ARRAY'S SIZE (nsm; ABI: mppi_onchip_spill_elems, restated by tests/test_abi.py) is that of the kernel without resident rows:
+  // there the wave's last `dls` local super-steps were generated a second time instead of waiting in memory -- whole tiles, as many as
+  // bring the regenerated share closest to 0.32 of the real super-steps beyond registers and LDS (profiles/r06_k_onchip_pair_check.txt).
+  // MPPI_PAIR_TAIL=0 still runs exactly that split.  MPPI_PAIR_DLS in the environment overrides the regenerated count of either
+  // split (measurements; any value).
   const int after = g.ntl * g.SW - g.KR - nsl;                        // local super-steps beyond registers and LDS, padding included
-  static const int forced = [] { const char* e = getenv("MPPI_PAIR_DLS"); return (e && *e) ? atoi(e) : -1; }();
+  // (read at every call, like MPPI_PAIR_TAIL: tests and sweeps change it inside one process)
+  const char* fe = getenv("MPPI_PAIR_DLS");
+  const int forced = (fe && *fe) ? atoi(fe) : -1;
   int dls = 0;
   if (after > 0) {
     auto real = [&](int ls) { return ls < g.nls && ((2 * (ls / g.CH)) * g.CH + ls % g.CH) < g.nss; };
@@ -186,7 +202,26 @@ static inline OnChipPairGeometry onchip_pair_geometry(int nu, int nx, int Tn, bo
     if (forced >= 0) dls = forced < after ? forced : after;
   }
   g.nsm = (after > 0 ? after : 0) - dls;
-  g.smem = (size_t)fixed + (size_t)nsl * g.P4 * 2 * BLOCK * 16;
+  g.nres = 0;
+  g.nmem = g.nsm;
+  g.nregen = dls;
+  if (tail != 0 && after > 0) {
+    // Resident: what of the last chunk lies beyond registers and LDS (all CH super-steps but for the shortest horizons).  Of the
+    // `mid` local super-steps between LDS and the resident ones the last rg are generated a second time, the others wait in memory;
+    // the weighting phase is bound either by the fetch of the memory rows or by its VALU work (column sums + second generation),
+    // side by side.  Measured at C3 (mid = 18; profiles/pair_tail_bench.txt, K1 device span): rg = 0 / 2 / 3 / 4 / 5 / 6 / 8 ->
+    // 58.8 / 58.0 / 56.8 / 57.0 / 57.4 / 58.4 / 59.5 us -- a sixth of them, rounded; splits inside a tile are the kernel's `mix` tile.
+    const int beyond = g.nls - g.KR - nsl;
+    g.nres = beyond < g.CH ? (beyond > 0 ? beyond : 0) : g.CH;
+    const int mid = g.nls - g.nres - g.KR - nsl, pad = g.ntl * g.SW - g.nls;
+    int rg = (mid + 3) / 6;
+    if (forced >= 0) rg = forced;
+    if (rg > mid) rg = mid;
+    if (mid - rg > g.nsm) rg = mid - g.nsm;                             // (never more rows than the array was sized for)
+    g.nmem = mid - rg;
+    g.nregen = rg + pad;
+  }
+  g.smem =(size_t)fixed + (size_t)nsl * g.P4 * 2 * BLOCK * 16;
   return g;
 }
 

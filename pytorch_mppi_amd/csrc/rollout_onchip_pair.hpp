@@ -9,7 +9,8 @@
 //   * a workgroup is 8 waves for the same 256 samples; waves p and p + 4 (one SIMD) are a PAIR, lane l of both is sample 64 p + l;
 //   * the horizon's super-steps go to the two waves in alternating chunks of CH (= the rows generated together): wave A (h = 0)
 //     owns chunks 0, 2, 4 ..., wave B (h = 1) chunks 1, 3, 5 ...  Each wave generates, bounds and KEEPS the rows of its chunks -- the
-//     first KR local super-steps in its registers, then LDS, then the spill array -- and later forms the column sums of exactly those
+//     first KR local super-steps in its registers, then LDS, then the spill array; the chunk of the last iteration simply stays in
+//     the generator's registers (MPPI_PAIR_TAIL) -- and later forms the column sums of exactly those
 //     rows: generation, keeping and the weighting phase are independent per (sample, row) and split without any exchange;
 //   * the rollout is sequential in t.  The state (and the running cost and the action cost accumulated so far, so that every sum is
 //     taken in the order the one-wave kernel takes it) goes from wave to wave through LDS at every chunk boundary, behind a progress
@@ -60,7 +61,7 @@ struct OnChipRowG {
 // PLAIN: no |noise| cost, u_scale == 1, no SMPPI terms (the common case, compiled without them); PLAIN = false: those terms as the
 // one-wave kernel applies them, and the previous timestep's action (the smoothness cost's operand) in the hand-over
 template <class Model, bool SEVEN = false, bool PLAIN = true>
-__global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const KArgs<float> a, const int nsl, const int nsm) {
+__global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const KArgs<float> a, const int nsl, const int nsm, const int nres) {
   using T = float;
   constexpr int NX = Model::NX, NU = Model::NU;
   using OP = OnChipPair<NU, PLAIN>;
@@ -134,11 +135,19 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
 #pragma unroll
   for (int n = 0; n < NU; ++n) vprev[n] = T(0);
   T rollout, pert;
+  // The wave's last `nres` local super-steps -- [R0, nls), rows of the chunk it generates in the last iteration -- are RESIDENT: their
+  // bounded noise is still in `zb` when the loop ends (the generator's live set -- vb, the Philox temporaries, x -- is dead by then),
+  // so they are neither kept anywhere nor generated a second time; the weighting phase reduces them as a tile of their own.  `zb`
+  // is declared out here for that alone: every iteration that owns a chunk overwrites all of it first thing, the loop body's live
+  // set is what it was.  (onchip_pair_geometry: M1 <= R0, the rows that wait in memory end in front of the resident ones.)
+  const int R0 = nres > 0 ? nls - nres : ntl * SW;
+  const bool res = nres > 0 && (2 * (nit - 1) + h) * CH < nss;           // this wave owns a chunk in the last iteration (wave-uniform)
+  T zb[CH][P4 * 4];
 
   for (int it = 0; it < nit; ++it) {
     const int c = 2 * it + h, ss0 = c * CH;
     const bool own = ss0 < nss;                                          // (the odd wave may have one chunk fewer)
-    T zb[CH][P4 * 4], vb[CH][P4 * 4];
+    T vb[CH][P4 * 4];
     if (own) {
 #pragma unroll
       for (int b = 0; b < CH; ++b) {
@@ -234,7 +243,8 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
     }
   }
   // local tiles: [0, tA) registers | [tA, tB) LDS | [tB, tC) memory | tile tC: its first `mix` super-steps memory, the rest -- and
-  // every later tile -- generated a second time (nsm need not be whole tiles: the split that balances fetch and VALU is not)
+  // every later tile -- generated a second time (nsm need not be whole tiles: the split that balances fetch and VALU is not), but
+  // for the resident local super-steps [R0, nls), which are neither
   const int tA = ntl < KT ? ntl : KT;
   const int tB = tA + nsl / SW < ntl ? tA + nsl / SW : ntl;
   const int tC = tB + nsm / SW < ntl ? tB + nsm / SW : ntl;
@@ -252,6 +262,13 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
   for (int ls = 0; ls < nls; ++ls) nreal += ((2 * (ls / CH) + h) * CH + ls % CH) < nss ? P4 : 0;
   const int nstored = nreal < M1 * P4 ? nreal : M1 * P4;                 // local rows [M0 P4, nstored) are in the array
   auto fetch = [&](int tile) __attribute__((always_inline)) {
+    // a wave that stored nothing (all its rows fit registers + LDS) loads nothing: `nstored - 1` would be a row in front of its
+    // workgroup's part of the array.  (Wave-uniform; its tiles' rows are all `!real` below.)
+    if (nstored <= tB * TRW) {
+#pragma unroll
+      for (int i = 0; i < TRW; ++i) pf[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < TRW; ++i) {
       // (a row never stored is not fetched: the last stored row is read again -- a hit -- and not used below.  No branch: the rows
@@ -262,7 +279,7 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
   };
   // the first tile that waited in memory takes off now: it flies while the partner finishes the last chunk and the workgroup
   // agrees on its minimum (whether this wave's weights are all zero is not known yet: a dead wave fetches this one tile in vain)
-  if (mt < tM && nstored > tB * TRW) fetch(mt);
+  if (mt < tM) fetch(mt);
   // every chunk rolled out: the last hand-over holds the final state and the two cost sums
   while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < nch) __builtin_amdgcn_s_sleep(1);
   {
@@ -308,9 +325,31 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
     });
     column_sums(tile, e);
   };
+  // tiles from ntE on hold resident rows and padding only: no pass
+  const int ntE = nres > 0 ? (R0 + SW - 1) / SW : ntl;
   if (!live) {
     for (int tile = 0; tile < ntl; ++tile) ex[(wv8 * ntl + tile) * 64 + lane] = T(0);
   } else {
+    if (res) {
+      // the resident rows first, while nothing else of the weighting phase is live beside keepR and the tile in flight: one tile of
+      // CH P4 rows (a column's sum does not depend on where it sits in its tile), each sum to the slot of its row's own tile.  Rows
+      // of the chunk that registers or LDS hold (a short horizon: ls < R0) and rows past the horizon contribute zero here.
+      constexpr int RC = CH * P4 * 4;
+      static_assert(RC <= 64, "the resident chunk is one reduction");
+      const int ls0 = (nit - 1) * CH, ssr = (2 * (nit - 1) + h) * CH;
+      T acc[64];
+#pragma unroll
+      for (int i = RC; i < 64; ++i) acc[i] = T(0);
+#pragma unroll
+      for (int b = 0; b < CH; ++b) {
+        const bool in = ls0 + b >= R0 && ssr + b < nss;
+#pragma unroll
+        for (int q = 0; q < P4 * 4; ++q) acc[b * P4 * 4 + q] = in ? wk * zb[b][q] : T(0);
+      }
+      const T s = wave_reduce_transpose64<float>(acc);
+      const int ls = ls0 + lane / (P4 * 4), lr = ls * P4 + (lane % (P4 * 4)) / 4;
+      if (lane < RC && ls >= R0) ex[(wv8 * ntl + lr / TRW) * 64 + (lr % TRW) * 4 + (lane & 3)] = s;
+    }
     for (int tile = 0; tile < tA; ++tile) from_registers(tile);
     for (int tile = tA; tile < tB; ++tile) {
       T e[TRW][4];
@@ -326,15 +365,16 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
     // column sums and the second generation, two waves per SIMD); the two proceed side by side, a memory tile's successor in
     // flight while a regenerated tile is computed, and the launcher picks the split that makes the larger of them smallest
     // (onchip_pair_geometry; profiles/r06_h_onchip_pair_check.txt, r06_k_onchip_pair_check.txt: everything fetched 67.1 us, the last two
-    // tiles generated again 60.4, splits inside a tile 62.3-62.4).
+    // tiles generated again 60.4, splits inside a tile 62.3-62.4; with the last chunk resident, profiles/pair_tail_bench.txt: 3 of the
+    // 18 super-steps between LDS and the resident chunk generated again 56.4-57.0 us against 58.6-59.1 on the same machine).
     // (The one-wave kernel found all-fetch best: there a second generation runs at one wave per SIMD.)
     int kd = blockIdx.x * K1_BLOCK + s256;
     asm volatile("" : "+v"(kd));
     const long long kgd = a.k_offset + (kd < a.K ? kd : a.K - 1);
     int dt = tM;                                                         // the next tile generated again in full
-    for (int step = 0; mt < tM || dt < ntl; ++step) {
+    for (int step = 0; mt < tM || dt < ntE; ++step) {
       // one body for every kind of tile: its first m super-steps out of `pf`, the rest generated again
-      const bool from_memory = mt < tM && ((step & 1) == 0 || dt >= ntl);
+      const bool from_memory = mt < tM && ((step & 1) == 0 || dt >= ntE);
       const int tile = from_memory ? mt : dt;
       const int m = from_memory ? (mt < tC ? SW : mix) : 0;
       T acc[64];                                                         // (the products go straight into the reduction's operands)
@@ -354,7 +394,7 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
             acc[(g * P4 + i) * 4 + 2] = real ? wk * q4.z : T(0);
             acc[(g * P4 + i) * 4 + 3] = real ? wk * q4.w : T(0);
           }
-        } else if (ss < nss) {
+        } else if (ss < nss && ls < R0) {
           T zg[P4 * 4], vg[P4 * 4];
 #pragma unroll
           for (int i = 0; i < P4; ++i) {
@@ -377,7 +417,10 @@ __global__ void __launch_bounds__(2 * K1_BLOCK) rollout_onchip_pair_kernel(const
       } else {
         ++dt;
       }
-      ex[(wv8 * ntl + tile) * 64 + lane] = wave_reduce_transpose64<float>(acc);
+      const T s = wave_reduce_transpose64<float>(acc);
+      // (a resident row's slot has its sum already; R0 >= nls without resident rows)
+      const int lsl = (tile * TRW + (lane >> 2)) / P4;
+      if (!(lane < TC && lsl >= R0 && lsl < nls)) ex[(wv8 * ntl + tile) * 64 + lane] = s;
     }
   }
   __syncthreads();
@@ -433,11 +476,12 @@ static int launch_rollout_onchip_pair(const KArgs<float>& a, hipStream_t st) {
   using OP = OnChipPair<NU, true>;
   if (a.spill == nullptr || a.diag == 0) return -1;
   const bool plain = !a.abs_cost && a.u_scale == 1.f && a.e_scale == 1.f && a.smooth_w == 0.f && a.B == nullptr;
-  const OnChipPairGeometry g = onchip_pair_geometry(NU, NX, a.Tn, plain);
+  const OnChipPairGeometry g = onchip_pair_geometry(NU, NX, a.Tn, plain, onchip_pair_tail());
   if (!g.ok || g.P4 != OP::P4 || g.TT != OP::TT || g.SW != OP::SW || g.KR != OP::KR ||
       g.CH != (plain ? OnChipPair<NU, true>::CH : OnChipPair<NU, false>::CH)) return -1;
   if (g.nch < 4) return -1;                                            // a horizon of fewer than four chunks: nothing to alternate
-  if ((long long)g.nsm * g.P4 * a.nkc * 2 * K1_BLOCK * 4 > a.spill_cap) return -1;     // the caller's array is the one-wave form's size
+  // the caller's array is the one-wave form's size (the kernel uses g.nmem <= g.nsm rows of it: the check stays the array's)
+  if ((long long)g.nsm * g.P4 * a.nkc * 2 * K1_BLOCK * 4 > a.spill_cap) return -1;
   const dim3 grid(a.nkc), block(2 * K1_BLOCK);
   KArgs<float> b = a;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -446,8 +490,8 @@ static int launch_rollout_onchip_pair(const KArgs<float>& a, hipStream_t st) {
 #define MPPI_PAIR_LAUNCH(KERNEL)                                                                                  \
   do {                                                                                                            \
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    if (ev1 != nullptr) hipExtLaunchKernelGGL(KERNEL, grid, block, smem, st, ev0, ev1, 0, b, g.nsl, g.nsm);       \
-    else hipLaunchKernelGGL(KERNEL, grid, block, smem, st, b, g.nsl, g.nsm);                                      \
+    if (ev1 != nullptr) hipExtLaunchKernelGGL(KERNEL, grid, block, smem, st, ev0, ev1, 0, b, g.nsl, g.nmem, g.nres); \
+    else hipLaunchKernelGGL(KERNEL, grid, block, smem, st, b, g.nsl, g.nmem, g.nres);                             \
   } while (0)
   if (a.seven) {
     if constexpr (onchip_seven_ok<Model>::value) {
