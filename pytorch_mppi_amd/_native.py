@@ -19,6 +19,7 @@ NEXT_DRAW_TORCH, NEXT_DRAW_PHILOX = 0, 1                                       #
 E_DIST = -4
 E_GROUP_PEER = -5
 MODEL_NONE, MODEL_PENDULUM, MODEL_INTEGRATOR, MODEL_LINEAR_GOAL, MODEL_MLP = 0, 1, 2, 3, 4
+MODEL_MLP2 = 5             # two hidden layers (csrc/mlp_deep.hpp; in include/mppi_amd.h from the next ABI bump)
 MODEL_CUSTOM_BASE = 100
 MODEL_FLAG_EXACT_FP32 = 1
 MODEL_FLAG_NO_WIDE = 2
@@ -128,6 +129,7 @@ SYMBOLS = {
 # SYMBOLS, at the next ABI bump)
 EXTRA_SYMBOLS = {
     "mppi_stat_mlp_split32_launches": (C.c_int64, []),
+    "mppi_stat_mlp_deep_launches": (C.c_int64, []),        # (csrc/mlp_deep.hpp)
     # (csrc/capi.hip: the two-wave on-chip kernel's split of a wave's rows -- registers / LDS / memory / resident / regenerated)
     "mppi_onchip_pair_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
 }

@@ -313,7 +313,7 @@ class Draws:
             return False
         ok = (type(self).__name__ in ("MPPI", "SMPPI") and self.dtype == torch.float32 and self.M == 1
               and self.specific_action_sampler is None and Tn == self.T and not self._needs_generic()
-              and self._model.model_id != N.MODEL_MLP)      # the dense MLP has its own matrix-core K1
+              and self._model.model_id not in (N.MODEL_MLP, N.MODEL_MLP2))  # the dense MLPs have their own matrix-core K1
         if not ok:
             return False
         if not self._diagonal_sigma:

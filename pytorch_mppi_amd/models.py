@@ -260,6 +260,79 @@ class MLPResidual(NativeModel):
                 + (self.q_control.to(state.device, state.dtype) * action ** 2).sum(dim=-1))
 
 
+# (nx, nu) with an instantiation of the two-hidden-layer matrix-core kernel (csrc/rollout_mlp_deep.hip MPPI_DEEP_DIMS)
+MLP2_MATRIX_CORE_SHAPES = ((16, 4), (12, 6), (2, 1))
+
+
+class MLPResidual2(NativeModel):
+    """x' = x + res_scale * (W3 tanh(W2 tanh(W1 [x;u] + b1) + b2) + b3): the residual network with TWO hidden layers, with the
+    diagonal quadratic running cost of `MLPResidual`.  The kernels see both hidden layers at ONE width `hidden`: 32 / 64 / 128
+    (csrc/rollout_mlp_deep.hip, the matrix cores) where the wider layer fits, else the wider layer's own width rounded up to the
+    per-lane kernel's block of 32 units.  Padding units have zero weights in and out and zero bias."""
+    model_id = N.MODEL_MLP2
+    # the per-lane kernels keep one rolled copy of the step and serve one state rollout per action sequence (their multi-rollout
+    # form spills registers, csrc/rollout_mlp2.hip): rollout_samples > 1 runs the callback loop
+    heavy = True
+
+    def __init__(self, W1, b1, W2, b2, W3, b3, nx, nu, res_scale=0.1, q_state=None, q_control=None):
+        super().__init__()
+        self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = (torch.as_tensor(t) for t in (W1, b1, W2, b2, W3, b3))
+        self.nx, self.nu = int(nx), int(nu)
+        self.hidden_units = (int(self.W1.shape[0]), int(self.W2.shape[0]))
+        widest = max(self.hidden_units)
+        fits = [w for w in (32, 64, 128) if widest <= w] if (self.nx, self.nu) in MLP2_MATRIX_CORE_SHAPES else []
+        self.hidden = fits[0] if fits else -(-widest // 32) * 32
+        self.res_scale = float(res_scale)
+        self.q_state = torch.ones(self.nx, dtype=torch.float64) if q_state is None else torch.as_tensor(q_state,
+                dtype=torch.float64).reshape(-1)
+        self.q_control = torch.zeros(self.nu, dtype=torch.float64) if q_control is None else torch.as_tensor(q_control,
+                dtype=torch.float64).reshape(-1)
+        h1, h2 = self.hidden_units
+        assert self.W1.shape == (h1, self.nx + self.nu) and self.W2.shape == (h2, h1) and self.W3.shape == (self.nx, h2)
+        assert self.b1.numel() == h1 and self.b2.numel() == h2 and self.b3.numel() == self.nx
+        assert self.q_state.numel() == self.nx and self.q_control.numel() == self.nu
+        self._plain_cost = q_state is None and q_control is None
+
+    def flags(self):
+        """The matrix-core kernel runs both 16-bit layers on two-piece fp16 operands: the folded weights -2 (2 log2 e) W2 and
+        -2 W3 must stay inside fp16's range.  Weights beyond it -- checked every time the parameter version changes -- select
+        the per-lane kernel, which has no such limit."""
+        if getattr(self, "_flags_version", None) != self._param_version:
+            folded = max(4.0 * math.log2(math.e) * float(self.W2.abs().max()), 2.0 * float(self.W3.abs().max()))
+            self._flags = N.MODEL_FLAG_EXACT_FP32 if folded >= 6.0e4 else 0
+            self._flags_version = self._param_version
+        return self._flags
+
+    @classmethod
+    def random(cls, nx, nu, hidden1, hidden2, seed=2, dtype=torch.float32, res_scale=0.1):
+        """torch.nn.Linear default initialisation under a private generator state."""
+        g = torch.random.get_rng_state()
+        torch.manual_seed(seed)
+        ls = [torch.nn.Linear(nx + nu, hidden1), torch.nn.Linear(hidden1, hidden2), torch.nn.Linear(hidden2, nx)]
+        torch.random.set_rng_state(g)
+        with torch.no_grad():
+            wb = [t.detach().to(dtype).clone() for l in ls for t in (l.weight, l.bias)]
+        return cls(*wb, nx, nu, res_scale)
+
+    def _param_list(self):
+        """csrc/mlp_deep.hpp: W1 (H,nx+nu) | b1 (H) | W2T (H,H) | b2 (H) | W3T (H,nx) | b3 (nx) | s | qx | qu"""
+        H, (h1, h2) = self.hidden, self.hidden_units
+        W1, b1, W2T, b2, W3T = (torch.zeros(*s, dtype=torch.float64) for s in ((H, self.nx + self.nu), (H,), (H, H), (H,),
+                (H, self.nx)))
+        W1[:h1], b1[:h1], W2T[:h1, :h2], b2[:h2], W3T[:h2] = (t.detach().to("cpu", torch.float64) for t in (self.W1, self.b1,
+                self.W2.T, self.b2, self.W3.T))
+        return [W1, b1, W2T, b2, W3T, self.b3, torch.tensor([self.res_scale], dtype=torch.float64), self.q_state,
+                self.q_control]
+
+    def dynamics(self, state, action, t=None):
+        W1, b1, W2, b2, W3, b3 = (t.to(state.device, state.dtype) for t in (self.W1, self.b1, self.W2, self.b2, self.W3,
+                self.b3))
+        h = torch.tanh(torch.tanh(torch.cat((state, action), dim=1) @ W1.T + b1) @ W2.T + b2)
+        return self._noisy(state + self.res_scale * (h @ W3.T + b3))
+
+    running_cost = MLPResidual.running_cost
+
+
 def native_model_of(dynamics, running_cost, terminal_state_cost=None):
     """The NativeModel whose bound methods were passed as the reference-style callables, or None."""
     m = dynamics if isinstance(dynamics, NativeModel) else getattr(dynamics, "__self__", None)
