@@ -130,6 +130,7 @@ SYMBOLS = {
 EXTRA_SYMBOLS = {
     "mppi_stat_mlp_split32_launches": (C.c_int64, []),
     "mppi_stat_mlp_deep_launches": (C.c_int64, []),        # (csrc/mlp_deep.hpp)
+    "mppi_stat_mlp_split_multi_launches": (C.c_int64, []),  # (csrc/mlp_split_multi.hpp)
     # (csrc/capi.hip: the two-wave on-chip kernel's split of a wave's rows -- registers / LDS / memory / resident / regenerated)
     "mppi_onchip_pair_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
 }

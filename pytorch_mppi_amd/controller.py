@@ -539,6 +539,14 @@ class MPPI(Draws, Forms, JitGlue):
             self.ktn_direct = False            # no in-place instantiation for this model: convert from now on
             self._convert_noise(p)
             rc = launch()
+        if rc == N.E_UNSUPPORTED and p.noise_src == N.NOISE_PHILOX and p.z and self.M > 1:
+            # M > 1 with the rows left to K1 (philox_fill = False): the matrix-core MLP kernel that generates them refused the
+            # launch (MPPI_MLP_MULTI=0 / MPPI_MLP_VALU / MPPI_MLP_EXACT, weights beyond its operand range, tables beyond its
+            # LDS) and the per-lane form reads its rows from memory -- the generator launch after all.  Nothing was launched
+            N.check(lib.mppi_noise_fill_philox(C.byref(p), p.z, st), "mppi_noise_fill_philox")
+            p.noise_src = N.NOISE_TNK4
+            self.last_draw = "philox-fill"
+            rc = launch()
         N.check(rc, "mppi_command")
         self._launched(p, int(lib.mppi_last_command_form()), int(lib.mppi_last_next_draw()))
 

@@ -11,6 +11,7 @@
 #include "dispatch.hpp"
 #include "mlp_deep.hpp"      // MPPI_MODEL_MLP2, its blob and mppi_stat_mlp_deep_launches (rollout_mlp_deep.hip, rollout_mlp2.hip)
 #include "mlp_split32.hpp"   // mppi_stat_mlp_split32_launches: defined by rollout_mlp_split32.hip, part of this C-ABI
+#include "mlp_split_multi.hpp"   // mppi_stat_mlp_split_multi_launches: defined by rollout_mlp_split_multi.hip, part of this C-ABI
 #include "update.hpp"
 
 using namespace mppi;

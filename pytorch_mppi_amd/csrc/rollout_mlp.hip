@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include "dispatch.hpp"
 #include "mlp_split32.hpp"
+#include "mlp_split_multi.hpp"
 #include "rollout.hpp"
 namespace mppi {
 // One translation unit per (nx,nu) pair (MPPI_MLP_GROUP, set by _build.py; chained like rollout_integrator.hip): the per-lane
@@ -112,6 +113,17 @@ int rollout_mlp(const KArgs<float>& a, hipStream_t st) {
     const int r = rollout_mlp_split32(a, st);
     if (r != MPPI_E_UNSUPPORTED) return r;
     // (rows it does not read, or a horizon whose tables do not fit the LDS beside the layer-1 weights: per lane)
+  }
+  if (!force_valu && !force_exact && a.M >= 2 && a.M <= PROCESS_NOISE_MM && a.states == nullptr &&
+      mlp_split_multi_supported(a.nx, a.nu, a.hidden)) {
+    // M = 2..4 state rollouts per action sequence, nx <= 16: one wave per copy on the split-operand kernel
+    // (rollout_mlp_split_multi.hip).  MPPI_MLP_MULTI=0 (read per launch): the per-lane copies, for A/B
+    const char* fm = getenv("MPPI_MLP_MULTI");
+    if (!(fm != nullptr && fm[0] == '0')) {
+      const int r = rollout_mlp_split_multi(a, st);
+      if (r != MPPI_E_UNSUPPORTED) return r;
+      // (rows it does not read, several environments, a horizon whose tables do not fit its LDS: per lane)
+    }
   }
   if (!force_valu && a.M == 1 && a.states == nullptr) {
     const bool use_split =!force_exact && mlp_split_supported(a.nx, a.nu, a.hidden);

@@ -124,7 +124,14 @@ class Draws:
                 # and costs one launch (~4 us): it wins from ~16 rows per sample on (tools/k_sweep.py)
                 fill = self.philox_fill if self.philox_fill is not None else rows4 >= 16
                 if self.M > 1 and not self._needs_generic():
-                    fill = True            # the multi-rollout K1 reads its rows from memory
+                    # the multi-rollout K1 reads its rows from memory -- but for the matrix-core MLP kernel of M copies
+                    # (csrc/rollout_mlp_split_multi.hip, nu = 4), which generates them on request (philox_fill = False; where
+                    # that kernel refuses the launch, controller._launch_prepared fills the rows and launches again).  Not
+                    # KMPPI's support-point stream
+                    m = self._model
+                    fill = not (self.philox_fill is False and m.model_id == N.MODEL_MLP and (self.nx, nu) == (16, 4)
+                                and m.hidden in (64, 128, 256) and self.dtype == torch.float32 and Tn == self.T
+                                and getattr(self, "num_support_pts", None) is None)
                 self.last_draw = "philox-fill" if fill else "philox-k1"
                 pf, self._pf_rows = self._pf_rows, None
                 self._next_armed = None

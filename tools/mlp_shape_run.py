@@ -7,7 +7,11 @@ matrix-pipe busy share = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 
 environment: its per-lane kernel).  `--callables`: the same network handed over as plain torch callables with auto_jit -- the
 tracer's dense-layer route (csrc/mlp_wide.hpp).  Only with one of these two (the plain form stays what the committed counter passes
 ran): one more warm-up command, the engine's device stamps, and one JSON line: ms per command (wall clock, synchronised) and the K1 launch
-time from the engine's device stamps where the launch carries them."""
+time from the engine's device stamps where the launch carries them.
+
+`--rollout-samples M --process-noise SD`: the stochastic model (`with_process_noise(SD)`) with M state rollouts per action sequence
+(csrc/rollout_mlp_split_multi.hip; MPPI_MLP_MULTI=0 in the environment: the per-lane copies) timed BESIDE the deterministic M = 1
+launch of the same run -- one JSON line with both K1 spans and their ratio (claim ratios within one run only)."""
 import json
 import os
 import sys
@@ -24,6 +28,15 @@ if "--deep" in argv:
     i = argv.index("--deep")
     deep = int(argv[i + 1])
     del argv[i:i + 2]
+multi, proc_sd = 0, 0.05
+for flag in ("--rollout-samples", "--process-noise"):
+    if flag in argv:
+        i = argv.index(flag)
+        if flag == "--rollout-samples":
+            multi = int(argv[i + 1])
+        else:
+            proc_sd = float(argv[i + 1])
+        del argv[i:i + 2]
 callables = "--callables" in argv
 argv = [v for v in argv if v != "--callables"]
 nx, nu, H = (int(v) for v in argv[:3])
@@ -51,6 +64,32 @@ x = torch.randn(nx).cuda()
 c.command(x)
 c.lambda_ = float(c.cost_total.float().std())
 lib = N.lib()
+if multi:
+    noisy = pm.models.MLPResidual.random(nx, nu, H, seed=2).with_process_noise(torch.full((nx,), proc_sd))
+    cm = pm.MPPI(noisy.dynamics, noisy.running_cost, nx, torch.eye(nu), num_samples=K, horizon=T, device="cuda", lambda_=c.lambda_,
+                 U_init=torch.randn(T, nu) * 0.02, rng="philox", seed=1234, rollout_samples=multi, rollout_var_cost=0.3,
+                 rollout_var_discount=0.9)
+    assert not cm._needs_generic()
+    out = {"shape": [nx, nu, H], "M": multi, "process_noise": proc_sd, "commands": n, "MPPI_MLP_MULTI": os.environ.get("MPPI_MLP_MULTI")}
+    for name, ctrl in (("m1", c), ("multi", cm), ("m1_again", c)):
+        for _ in range(2):
+            ctrl.command(x)
+        m0 = int(lib.mppi_stat_mlp_split_multi_launches())
+        lib.mppi_profile_enable(1 << 30)            # device stamps only
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            ctrl.command(x)
+        torch.cuda.synchronize()
+        out[name + "_ms_per_command"] = round((time.perf_counter() - t0) / n * 1e3, 4)
+        dv, _ = N.profile_read_launches()
+        lib.mppi_profile_enable(0)
+        out[name + "_k1_device_span_us"] = round(sum(dv) / len(dv), 1) if dv else None
+        out[name + "_split_multi_launches"] = int(lib.mppi_stat_mlp_split_multi_launches()) - m0
+    if out["m1_k1_device_span_us"] and out["multi_k1_device_span_us"]:
+        out["k1_ratio_multi_over_m1"] = round(out["multi_k1_device_span_us"] / out["m1_k1_device_span_us"], 3)
+    print(json.dumps(out))
+    sys.exit(0)
 if not (deep or callables):
     # the counter / trace passes over the one-hidden-layer shapes: plain launches, nothing but the commands
     n0 = int(lib.mppi_stat_mlp_split_launches())
