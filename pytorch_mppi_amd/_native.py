@@ -131,6 +131,9 @@ EXTRA_SYMBOLS = {
     "mppi_stat_mlp_split32_launches": (C.c_int64, []),
     "mppi_stat_mlp_deep_launches": (C.c_int64, []),        # (csrc/mlp_deep.hpp)
     "mppi_stat_mlp_split_multi_launches": (C.c_int64, []),  # (csrc/mlp_split_multi.hpp)
+    # (csrc/mlp_deep_multi.hpp: the two-hidden-layer model at rollout_samples 2..4 -- the launcher's static promise, its launches)
+    "mppi_mlp_deep_multi_supported": (C.c_int, [C.c_int32] * 6),
+    "mppi_stat_mlp_deep_multi_launches": (C.c_int64, []),
     # (csrc/capi.hip: the two-wave on-chip kernel's split of a wave's rows -- registers / LDS / memory / resident / regenerated)
     "mppi_onchip_pair_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
 }
@@ -210,6 +213,15 @@ def noise_rows4(T, nu):
 def noise_pitch(K, dtype_code):
     """Row pitch (samples) of a TNK4 noise array for K samples (include/mppi_amd.h)."""
     return int(lib().mppi_noise_pitch(int(K), int(dtype_code)))
+
+
+def mlp_deep_multi_supported(nx, nu, hidden, M, T, num_envs=1):
+    """Does csrc/rollout_mlp_deep_multi.hip take MODEL_MLP2 at M rollouts per sequence (fp32; csrc/mlp_deep_multi.hpp)?"""
+    k = ("dm", nx, nu, hidden, M, T, num_envs)
+    v = _PURE.get(k)
+    if v is None:
+        v = _PURE[k] = bool(lib().mppi_mlp_deep_multi_supported(int(nx), int(nu), int(hidden), int(M), int(T), int(num_envs)))
+    return v
 
 
 def model_supported(model_id, nx, nu, dtype_code, hidden=0):

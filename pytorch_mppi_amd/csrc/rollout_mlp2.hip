@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include "dispatch.hpp"
 #include "mlp_deep.hpp"
+#include "mlp_deep_multi.hpp"
 #include "rollout.hpp"
 namespace mppi {
 #ifndef MPPI_MLP2_GROUP
@@ -41,8 +42,8 @@ struct Mlp2Model {
   static constexpr int MB = sizeof(T) == 4 ? 32 : 16;   // accumulators per block: layer 1 is evaluated H / MB times per step
   static constexpr bool NO_KMPPI_FUSE = true;
   // one rolled copy of the step, one state rollout per action sequence (rollout.hpp model_heavy): the unrolled streams and the
-  // multi-rollout instantiations spill (40 VGPRs and 164 B of scratch at (16, 4)), so they are not built and rollout_samples > 1
-  // runs the callback loop (models.MLPResidual2.heavy)
+  // multi-rollout instantiations spill (40 VGPRs and 164 B of scratch at (16, 4)), so they are not built: rollout_samples > 1
+  // is the matrix-core kernel's alone (rollout_mlp_deep_multi.hip), else the callback loop (models.MLPResidual2.heavy)
   static constexpr bool HEAVY = true;
   // (one base pointer and offsets worked out where they are used: eight resident pointers cost the scalar registers the rollout
   //  streams of rollout.hpp need for their own tables)
@@ -170,6 +171,11 @@ int rollout_mlp2(const KArgs<float>& a, hipStream_t st) {
   const char* fv = getenv("MPPI_MLP_VALU");
   const bool force_valu = fv != nullptr && fv[0] == '1';
   const bool exact = (a.model_flags & MPPI_MODEL_FLAG_EXACT_FP32) != 0;
+  // M = 2..4 rollouts per sequence: one wave per copy on the matrix cores (rollout_mlp_deep_multi.hip), which also writes the
+  // visited states.  There is no per-lane form behind it (HEAVY above): what it refuses is refused (the host keeps such
+  // commands on the callback loop, forms._fused_multi_ok).  MPPI_MLP_VALU has nothing to select here and is not read: the A/B
+  // switch of this path is MPPI_MLP_MULTI=0, read by the host (back to the callback loop)
+  if (a.M > 1) return exact || a.noise_src == MPPI_NOISE_KTN ? MPPI_E_UNSUPPORTED : rollout_mlp_deep_multi(a, st);
   if (!force_valu && !exact && a.M == 1 && a.states == nullptr && mlp_deep_supported(a.nx, a.nu, a.hidden)) {
     // the kernel reads the engine's own layout: ask the caller to convert a (K,T,nu) draw
     if (a.noise_src == MPPI_NOISE_KTN) return MPPI_E_UNSUPPORTED;

@@ -32,6 +32,8 @@
 //            k-step p - 2
 //   tail     the last pair's activations around the output layer's last two k-steps
 // One persistent workgroup of 4 waves per CU over 128-sample chunks, two sample tiles per wave -- as the one-hidden-layer kernels.
+// TWIN: rollout_mlp_deep_multi.hip (M = 2..4, one wave per rollout copy) restates dp_interleave, the plane packing, the slot
+// lambdas and act_unit of this file: a fix to the pipeline here is a fix there, too (to be shared through a header).
 #include <hip/hip_ext.h>
 #include <atomic>
 #include "actions.hpp"

@@ -114,7 +114,9 @@ class Draws:
                         p.onchip_spill, p.onchip_spill_elems = _ptr(sp[1]), sp[1].numel()
                         p._keep["spill"] = sp[1]
                 return
-            if self.philox_store:
+            # (the two-hidden-layer model at M > 1 has one kernel, which reads its rows from memory: csrc/rollout_mlp_deep_multi.hip)
+            rows_only = self.M > 1 and getattr(self._model, "model_id", None) == N.MODEL_MLP2 and not self._needs_generic()
+            if self.philox_store or rows_only:
                 # generate once, keep the rows for K3 to re-read: Philox + Box-Muller costs more per
                 # element than an HBM read
                 rows4 = N.noise_rows4(Tn, nu)
@@ -127,7 +129,7 @@ class Draws:
                     # the multi-rollout K1 reads its rows from memory -- but for the matrix-core MLP kernel of M copies
                     # (csrc/rollout_mlp_split_multi.hip, nu = 4), which generates them on request (philox_fill = False; where
                     # that kernel refuses the launch, controller._launch_prepared fills the rows and launches again).  Not
-                    # KMPPI's support-point stream
+                    # KMPPI's support-point stream, and never the two-hidden-layer model (MODEL_MLP2: rows from memory only)
                     m = self._model
                     fill = not (self.philox_fill is False and m.model_id == N.MODEL_MLP and (self.nx, nu) == (16, 4)
                                 and m.hidden in (64, 128, 256) and self.dtype == torch.float32 and Tn == self.T

@@ -7,6 +7,7 @@ fused path and the callback path (`_needs_generic`), runs the callback path's ro
 derived
 public arrays."""
 import ctypes as C
+import os
 
 import torch
 
@@ -170,6 +171,9 @@ class Forms:
             return True
         s = self.specific_action_sampler
         key = (id(m), m.model_id, self.M, id(s), id(m.process_noise), self.nx, self.nu, self.dtype)
+        if self.M > 1 and m.model_id == N.MODEL_MLP2:
+            # ... and what _fused_multi_ok reads for this model on top: the weights' range, the horizon, Sigma's form, the switch
+            key += (m._param_version, m.hidden, self.T, self._diagonal_sigma, os.environ.get("MPPI_MLP_MULTI"))
         hit = self._generic_memo
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -197,7 +201,19 @@ class Forms:
         (its two-launch form: interpolated raw actions in memory), at most 4 copies of the state per lane; anything else
         runs
         the reference's callback loop."""
-        return (1 < self.M <= 4 and self.specific_action_sampler is None and not getattr(self._model, "heavy", False))
+        m = self._model
+        if not (1 < self.M <= 4 and self.specific_action_sampler is None):
+            return False
+        if getattr(m, "model_id", None) == N.MODEL_MLP2:
+            # the two-hidden-layer model has no per-lane form to fall back on at M > 1 (models.MLPResidual2.heavy): what its
+            # one-wave-per-copy matrix-core kernel takes is promised here, statically (csrc/mlp_deep_multi.hpp) -- fp32, weights
+            # within the kernel's fp16 operand range, a diagonal Sigma (rows read component-wise, the action cost one product
+            # per element; KMPPI's raw actions included).  MPPI_MLP_MULTI=0: the callback loop (A/B measurements; MPPI_MLP_VALU
+            # selects nothing at M > 1).  An `MPPI_Batched` never gets here (its M is 1)
+            return (self.dtype == torch.float32 and m.flags() == 0 and os.environ.get("MPPI_MLP_MULTI") != "0"
+                    and self._diagonal_sigma
+                    and N.mlp_deep_multi_supported(self.nx, self.nu, m.hidden, self.M, self.T))
+        return not getattr(m, "heavy", False)
 
     def _fused_state(self, per_sample):
         """Initial state as the fused kernels read it: (K_local,nx) rows or one (nx,) vector.  The

@@ -268,10 +268,15 @@ class MLPResidual2(NativeModel):
     """x' = x + res_scale * (W3 tanh(W2 tanh(W1 [x;u] + b1) + b2) + b3): the residual network with TWO hidden layers, with the
     diagonal quadratic running cost of `MLPResidual`.  The kernels see both hidden layers at ONE width `hidden`: 32 / 64 / 128
     (csrc/rollout_mlp_deep.hip, the matrix cores) where the wider layer fits, else the wider layer's own width rounded up to the
-    per-lane kernel's block of 32 units.  Padding units have zero weights in and out and zero bias."""
+    per-lane kernel's block of 32 units.  Padding units have zero weights in and out and zero bias.
+
+    `with_process_noise(sd)` and `rollout_samples` 2..4 stay on the matrix cores at those shapes and widths (fp32, a diagonal
+    Sigma, weights within fp16 range): one wave per rollout copy, csrc/rollout_mlp_deep_multi.hip.  Everything else at
+    rollout_samples > 1 runs the callback loop (forms._fused_multi_ok)."""
     model_id = N.MODEL_MLP2
     # the per-lane kernels keep one rolled copy of the step and serve one state rollout per action sequence (their multi-rollout
-    # form spills registers, csrc/rollout_mlp2.hip): rollout_samples > 1 runs the callback loop
+    # form spills registers, csrc/rollout_mlp2.hip): at rollout_samples > 1 there is no per-lane form to fall back on, and only
+    # what the matrix-core kernel of M copies promises statically leaves the callback loop (forms._fused_multi_ok)
     heavy = True
 
     def __init__(self, W1, b1, W2, b2, W3, b3, nx, nu, res_scale=0.1, q_state=None, q_control=None):

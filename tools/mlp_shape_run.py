@@ -11,7 +11,8 @@ time from the engine's device stamps where the launch carries them.
 
 `--rollout-samples M --process-noise SD`: the stochastic model (`with_process_noise(SD)`) with M state rollouts per action sequence
 (csrc/rollout_mlp_split_multi.hip; MPPI_MLP_MULTI=0 in the environment: the per-lane copies) timed BESIDE the deterministic M = 1
-launch of the same run -- one JSON line with both K1 spans and their ratio (claim ratios within one run only)."""
+launch of the same run -- one JSON line with both K1 spans and their ratio (claim ratios within one run only).  With `--deep H2`: the
+two-hidden-layer model (csrc/rollout_mlp_deep_multi.hip; MPPI_MLP_MULTI=0: the callback loop, which has no K1 launch)."""
 import json
 import os
 import sys
@@ -65,16 +66,21 @@ c.command(x)
 c.lambda_ = float(c.cost_total.float().std())
 lib = N.lib()
 if multi:
-    noisy = pm.models.MLPResidual.random(nx, nu, H, seed=2).with_process_noise(torch.full((nx,), proc_sd))
+    noisy = (pm.models.MLPResidual2.random(nx, nu, H, deep, seed=2) if deep else pm.models.MLPResidual.random(nx, nu, H, seed=2))
+    noisy.with_process_noise(torch.full((nx,), proc_sd))
+    stat = lib.mppi_stat_mlp_deep_multi_launches if deep else lib.mppi_stat_mlp_split_multi_launches
     cm = pm.MPPI(noisy.dynamics, noisy.running_cost, nx, torch.eye(nu), num_samples=K, horizon=T, device="cuda", lambda_=c.lambda_,
                  U_init=torch.randn(T, nu) * 0.02, rng="philox", seed=1234, rollout_samples=multi, rollout_var_cost=0.3,
                  rollout_var_discount=0.9)
-    assert not cm._needs_generic()
-    out = {"shape": [nx, nu, H], "M": multi, "process_noise": proc_sd, "commands": n, "MPPI_MLP_MULTI": os.environ.get("MPPI_MLP_MULTI")}
+    # (--deep under MPPI_MLP_MULTI=0 is the callback loop, with no K1 launch to stamp; everything else must be fused)
+    off = os.environ.get("MPPI_MLP_MULTI")
+    assert cm._needs_generic() == bool(deep and off == "0")
+    out = {"shape": [nx, nu, H] + ([deep] if deep else []), "M": multi, "callback_loop": bool(cm._needs_generic()),
+           "process_noise": proc_sd, "commands": n, "MPPI_MLP_MULTI": off}
     for name, ctrl in (("m1", c), ("multi", cm), ("m1_again", c)):
         for _ in range(2):
             ctrl.command(x)
-        m0 = int(lib.mppi_stat_mlp_split_multi_launches())
+        m0 = int(stat())
         lib.mppi_profile_enable(1 << 30)            # device stamps only
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -85,7 +91,7 @@ if multi:
         dv, _ = N.profile_read_launches()
         lib.mppi_profile_enable(0)
         out[name + "_k1_device_span_us"] = round(sum(dv) / len(dv), 1) if dv else None
-        out[name + "_split_multi_launches"] = int(lib.mppi_stat_mlp_split_multi_launches()) - m0
+        out[name + ("_deep_multi_launches" if deep else "_split_multi_launches")] = int(stat()) - m0
     if out["m1_k1_device_span_us"] and out["multi_k1_device_span_us"]:
         out["k1_ratio_multi_over_m1"] = round(out["multi_k1_device_span_us"] / out["m1_k1_device_span_us"], 3)
     print(json.dumps(out))
