@@ -19,14 +19,15 @@ OBJ_DIR = os.path.join(CSRC, "build" + SUFFIX)
 SOURCES = ["capi.hip", "dist.hip", "group.hip", "update.hip", "rollout_pendulum.hip", "rollout_integrator.hip",
            "rollout_linear_goal.hip", "rollout_mlp.hip", "rollout_mlp_mfma.hip", "rollout_mlp_split.hip",
                    "rollout_mlp_split32.hip", "rollout_mlp_split_multi.hip", "rollout_mlp_deep.hip", "rollout_mlp2.hip",
-           "rollout_mlp_deep_multi.hip",
+           "rollout_mlp_deep_multi.hip", "rollout_mlp_split32_multi.hip",
            "noise_torch.hip"]
 # translation units: (source, object name, extra flags).  The two heaviest sources are compiled as several units each
 # (groups of model dimensions selected with a define) so that the parallel build is not one long compile
 _GROUPS = {"rollout_integrator.hip": ("MPPI_INTEGRATOR_GROUP", 4), "rollout_linear_goal.hip": ("MPPI_LINEAR_GROUP", 3),
            "rollout_mlp.hip": ("MPPI_MLP_GROUP", 8), "rollout_mlp_split.hip": ("MPPI_SPLIT_GROUP", 2),
            "rollout_mlp2.hip": ("MPPI_MLP2_GROUP", 3), "rollout_mlp_split_multi.hip": ("MPPI_SPLIT_MULTI_GROUP", 2),
-           "rollout_mlp_deep_multi.hip": ("MPPI_DEEP_MULTI_GROUP", 3)}
+           "rollout_mlp_deep_multi.hip": ("MPPI_DEEP_MULTI_GROUP", 3),
+           "rollout_mlp_split32_multi.hip": ("MPPI_SPLIT32_MULTI_GROUP", 2)}
 # no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the units added since round 6: no faster than two scalar
 # instructions on gfx950 (see EXTRA), and the older units keep their flags, i.e. their code, as measured
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
@@ -53,6 +54,7 @@ def _units():
             "rollout_mlp_split_g1.o": 35, "rollout_mlp_g6.o": 90, "rollout_mlp_g7.o": 80, "rollout_mlp_split32.o": 45,
             "rollout_mlp_split_multi_g0.o": 60, "rollout_mlp_split_multi_g1.o": 60,
             "rollout_mlp_deep_multi_g0.o": 40, "rollout_mlp_deep_multi_g1.o": 40, "rollout_mlp_deep_multi_g2.o": 40,
+            "rollout_mlp_split32_multi_g0.o": 25, "rollout_mlp_split32_multi_g1.o": 25,
             "rollout_mlp_deep.o": 40, "rollout_mlp2_g0.o": 60, "rollout_mlp2_g1.o": 60, "rollout_mlp2_g2.o": 40}
     return sorted(units, key=lambda u: -cost.get(u[1], 5))
 # -ffp-contract=fast: mul+add pairs fuse into v_fma / v_pk_fma.  torch eager rounds twice where
@@ -78,6 +80,8 @@ EXTRA = {"update.hip": ["-mllvm", "-pragma-unroll-threshold=200000"],
          "rollout_mlp_deep.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] + NO_PK_F32,
          # its one-wave-per-copy form for M > 1 state rollouts: the same arithmetic, the same flags
          "rollout_mlp_deep_multi.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] + NO_PK_F32,
+         # the two-output-tile kernel's one-wave-per-copy form: the flags of rollout_mlp_split32.hip
+         "rollout_mlp_split32_multi.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] + NO_PK_F32,
          # the KMPPI-fused K1 (rollout_kmppi.hpp) pins 256 control points in the AGPRs and reads its 4 x nu
          # accumulator tile with the VALU: same flag for every unit that instantiates it (jit.py passes it too)
          "rollout_integrator.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

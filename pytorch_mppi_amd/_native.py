@@ -134,6 +134,9 @@ EXTRA_SYMBOLS = {
     # (csrc/mlp_deep_multi.hpp: the two-hidden-layer model at rollout_samples 2..4 -- the launcher's static promise, its launches)
     "mppi_mlp_deep_multi_supported": (C.c_int, [C.c_int32] * 6),
     "mppi_stat_mlp_deep_multi_launches": (C.c_int64, []),
+    # (csrc/mlp_split32_multi.hpp: MLPResidual with 16 < nx <= 32 at rollout_samples 2..4 -- the same pair)
+    "mppi_mlp_split32_multi_supported": (C.c_int, [C.c_int32] * 6),
+    "mppi_stat_mlp_split32_multi_launches": (C.c_int64, []),
     # (csrc/capi.hip: the two-wave on-chip kernel's split of a wave's rows -- registers / LDS / memory / resident / regenerated)
     "mppi_onchip_pair_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
 }
@@ -221,6 +224,16 @@ def mlp_deep_multi_supported(nx, nu, hidden, M, T, num_envs=1):
     v = _PURE.get(k)
     if v is None:
         v = _PURE[k] = bool(lib().mppi_mlp_deep_multi_supported(int(nx), int(nu), int(hidden), int(M), int(T), int(num_envs)))
+    return v
+
+
+def mlp_split32_multi_supported(nx, nu, hidden, M, T, num_envs=1):
+    """Does csrc/rollout_mlp_split32_multi.hip take MODEL_MLP with 16 < nx <= 32 at M rollouts per sequence (fp32;
+    csrc/mlp_split32_multi.hpp)?"""
+    k = ("s32m", nx, nu, hidden, M, T, num_envs)
+    v = _PURE.get(k)
+    if v is None:
+        v = _PURE[k] = bool(lib().mppi_mlp_split32_multi_supported(int(nx), int(nu), int(hidden), int(M), int(T), int(num_envs)))
     return v
 
 

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include "dispatch.hpp"
 #include "mlp_split32.hpp"
+#include "mlp_split32_multi.hpp"
 #include "mlp_split_multi.hpp"
 #include "rollout.hpp"
 namespace mppi {
@@ -68,7 +69,8 @@ int MPPI_NEXT(const KArgs<double>& a, hipStream_t st);
 #endif
 // More than 16 states: the per-lane kernels keep ONE rolled copy of the step (rollout.hpp model_heavy) and serve one state
 // rollout per action sequence -- the multi-rollout instantiations of these shapes spill vector registers (35 at (32, 8)), so
-// they are not built and M > 1 runs the callback loop (models.MLPResidual.heavy).
+// they are not built: M > 1 is the matrix-core kernel's alone (rollout_mlp_split32_multi.hip), else the callback loop
+// (models.MLPResidual.heavy).
 template <typename T, int NX, int NU>
 struct MlpModelRolled : MlpModel<T, NX, NU> {
   static constexpr bool HEAVY = true;
@@ -113,6 +115,14 @@ int rollout_mlp(const KArgs<float>& a, hipStream_t st) {
     const int r = rollout_mlp_split32(a, st);
     if (r != MPPI_E_UNSUPPORTED) return r;
     // (rows it does not read, or a horizon whose tables do not fit the LDS beside the layer-1 weights: per lane)
+  }
+  if (!force_exact && a.M >= 2 && a.M <= PROCESS_NOISE_MM && a.nx > 16 && mlp_split32_supported(a.nx, a.nu, a.hidden)) {
+    // M = 2..4 state rollouts per action sequence, 16 < nx <= 32: one wave per copy on the two-output-tile kernel
+    // (rollout_mlp_split32_multi.hip), which also writes the visited states.  There is no per-lane form behind it
+    // (MlpModelRolled above): what it refuses is refused, and MPPI_MLP_VALU has nothing to select.  MPPI_MLP_MULTI=0 (read per
+    // launch, and by the host: forms._fused_multi_ok): the callback loop, for A/B
+    const char* fm = getenv("MPPI_MLP_MULTI");
+    if (!(fm != nullptr && fm[0] == '0')) return rollout_mlp_split32_multi(a, st);
   }
   if (!force_valu && !force_exact && a.M >= 2 && a.M <= PROCESS_NOISE_MM && a.states == nullptr &&
       mlp_split_multi_supported(a.nx, a.nu, a.hidden)) {

@@ -114,8 +114,11 @@ class Draws:
                         p.onchip_spill, p.onchip_spill_elems = _ptr(sp[1]), sp[1].numel()
                         p._keep["spill"] = sp[1]
                 return
-            # (the two-hidden-layer model at M > 1 has one kernel, which reads its rows from memory: csrc/rollout_mlp_deep_multi.hip)
-            rows_only = self.M > 1 and getattr(self._model, "model_id", None) == N.MODEL_MLP2 and not self._needs_generic()
+            # (the two-hidden-layer model at M > 1 has one kernel, which reads its rows from memory: csrc/rollout_mlp_deep_multi.hip;
+            # so has MLPResidual beyond 16 states: csrc/rollout_mlp_split32_multi.hip)
+            mid = getattr(self._model, "model_id", None)
+            rows_only = (self.M > 1 and (mid == N.MODEL_MLP2 or (mid == N.MODEL_MLP and getattr(self._model, "heavy", False)))
+                         and not self._needs_generic())
             if self.philox_store or rows_only:
                 # generate once, keep the rows for K3 to re-read: Philox + Box-Muller costs more per
                 # element than an HBM read

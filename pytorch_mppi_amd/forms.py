@@ -171,7 +171,7 @@ class Forms:
             return True
         s = self.specific_action_sampler
         key = (id(m), m.model_id, self.M, id(s), id(m.process_noise), self.nx, self.nu, self.dtype)
-        if self.M > 1 and m.model_id == N.MODEL_MLP2:
+        if self.M > 1 and (m.model_id == N.MODEL_MLP2 or (m.model_id == N.MODEL_MLP and getattr(m, "heavy", False))):
             # ... and what _fused_multi_ok reads for this model on top: the weights' range, the horizon, Sigma's form, the switch
             key += (m._param_version, m.hidden, self.T, self._diagonal_sigma, os.environ.get("MPPI_MLP_MULTI"))
         hit = self._generic_memo
@@ -213,6 +213,12 @@ class Forms:
             return (self.dtype == torch.float32 and m.flags() == 0 and os.environ.get("MPPI_MLP_MULTI") != "0"
                     and self._diagonal_sigma
                     and N.mlp_deep_multi_supported(self.nx, self.nu, m.hidden, self.M, self.T))
+        if getattr(m, "model_id", None) == N.MODEL_MLP and getattr(m, "heavy", False):
+            # MLPResidual beyond 16 states: the same static promise for the two-output-tile kernel's one-wave-per-copy form
+            # (csrc/mlp_split32_multi.hpp), under the same conditions
+            return (self.dtype == torch.float32 and m.flags() == 0 and os.environ.get("MPPI_MLP_MULTI") != "0"
+                    and self._diagonal_sigma
+                    and N.mlp_split32_multi_supported(self.nx, self.nu, m.hidden, self.M, self.T))
         return not getattr(m, "heavy", False)
 
     def _fused_state(self, per_sample):

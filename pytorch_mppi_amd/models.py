@@ -196,7 +196,12 @@ class MLPResidual(NativeModel):
     """x' = x + res_scale * (W2 tanh(W1 [x;u] + b1) + b2) -- the 2-layer approximate-dynamics shape of
     /root/reference/tests/pendulum_approximate.py:47-67 -- with the diagonal quadratic running cost
     sum_i q_state[i] x_i^2 + sum_n q_control[n] u_n^2 (defaults 1 and 0: the plain sum x^2 of BASELINE
-    configs[3..4])."""
+    configs[3..4]).
+
+    More than 16 states (16 < nx <= 32): `with_process_noise(sd)` and `rollout_samples` 2..4 stay on the matrix cores at the
+    (nx, nu) of csrc/rollout_mlp_split32.hip and hidden <= 256 (fp32, a diagonal Sigma, weights within fp16 range): one wave
+    per rollout copy, csrc/rollout_mlp_split32_multi.hip, which also stores the visited states.  Everything else at nx > 16
+    and rollout_samples > 1 runs the callback loop (forms._fused_multi_ok)."""
     model_id = N.MODEL_MLP
 
     def __init__(self, W1, b1, W2, b2, nx, nu, res_scale=0.1, q_state=None, q_control=None):
@@ -208,7 +213,8 @@ class MLPResidual(NativeModel):
         self.hidden_units = int(self.W1.shape[0])
         self.hidden = mlp_kernel_width(nx, nu, self.hidden_units)
         # more than 16 states: the per-lane kernels are built for one state rollout per action sequence only (their
-        # multi-rollout form spills registers, csrc/rollout_mlp.hip) -- rollout_samples > 1 runs the callback loop
+        # multi-rollout form spills registers, csrc/rollout_mlp.hip) -- at rollout_samples > 1 only what the matrix-core kernel
+        # of M copies promises statically leaves the callback loop (forms._fused_multi_ok)
         self.heavy = self.nx > 16
         self.res_scale = float(res_scale)
         self.q_state = torch.ones(self.nx, dtype=torch.float64) if q_state is None else torch.as_tensor(q_state,

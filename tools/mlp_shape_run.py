@@ -12,7 +12,8 @@ time from the engine's device stamps where the launch carries them.
 `--rollout-samples M --process-noise SD`: the stochastic model (`with_process_noise(SD)`) with M state rollouts per action sequence
 (csrc/rollout_mlp_split_multi.hip; MPPI_MLP_MULTI=0 in the environment: the per-lane copies) timed BESIDE the deterministic M = 1
 launch of the same run -- one JSON line with both K1 spans and their ratio (claim ratios within one run only).  With `--deep H2`: the
-two-hidden-layer model (csrc/rollout_mlp_deep_multi.hip; MPPI_MLP_MULTI=0: the callback loop, which has no K1 launch)."""
+two-hidden-layer model (csrc/rollout_mlp_deep_multi.hip; MPPI_MLP_MULTI=0: the callback loop, which has no K1 launch).  With nx > 16:
+the two-output-tile model (csrc/rollout_mlp_split32_multi.hip; MPPI_MLP_MULTI=0: the callback loop again)."""
 import json
 import os
 import sys
@@ -68,13 +69,15 @@ lib = N.lib()
 if multi:
     noisy = (pm.models.MLPResidual2.random(nx, nu, H, deep, seed=2) if deep else pm.models.MLPResidual.random(nx, nu, H, seed=2))
     noisy.with_process_noise(torch.full((nx,), proc_sd))
-    stat = lib.mppi_stat_mlp_deep_multi_launches if deep else lib.mppi_stat_mlp_split_multi_launches
+    wide = not deep and nx > 16            # the two-output-tile model: csrc/rollout_mlp_split32_multi.hip, no per-lane copies behind it
+    stat = (lib.mppi_stat_mlp_deep_multi_launches if deep else
+            lib.mppi_stat_mlp_split32_multi_launches if wide else lib.mppi_stat_mlp_split_multi_launches)
     cm = pm.MPPI(noisy.dynamics, noisy.running_cost, nx, torch.eye(nu), num_samples=K, horizon=T, device="cuda", lambda_=c.lambda_,
                  U_init=torch.randn(T, nu) * 0.02, rng="philox", seed=1234, rollout_samples=multi, rollout_var_cost=0.3,
                  rollout_var_discount=0.9)
     # (--deep under MPPI_MLP_MULTI=0 is the callback loop, with no K1 launch to stamp; everything else must be fused)
     off = os.environ.get("MPPI_MLP_MULTI")
-    assert cm._needs_generic() == bool(deep and off == "0")
+    assert cm._needs_generic() == bool((deep or wide) and off == "0")
     out = {"shape": [nx, nu, H] + ([deep] if deep else []), "M": multi, "callback_loop": bool(cm._needs_generic()),
            "process_noise": proc_sd, "commands": n, "MPPI_MLP_MULTI": off}
     for name, ctrl in (("m1", c), ("multi", cm), ("m1_again", c)):
@@ -91,7 +94,7 @@ if multi:
         dv, _ = N.profile_read_launches()
         lib.mppi_profile_enable(0)
         out[name + "_k1_device_span_us"] = round(sum(dv) / len(dv), 1) if dv else None
-        out[name + ("_deep_multi_launches" if deep else "_split_multi_launches")] = int(stat()) - m0
+        out[name + ("_deep_multi_launches" if deep else "_split32_multi_launches" if wide else "_split_multi_launches")] = int(stat()) - m0
     if out["m1_k1_device_span_us"] and out["multi_k1_device_span_us"]:
         out["k1_ratio_multi_over_m1"] = round(out["multi_k1_device_span_us"] / out["m1_k1_device_span_us"], 3)
     print(json.dumps(out))
