@@ -631,6 +631,11 @@ class MPPI(Draws, Forms, JitGlue):
         (mppi.py:307-310, :329-331) -- or (M,K,T,nx) for M > 1 rollouts, where the reference always
         stores them (:349-350, :366)."""
         want = self.terminal_state_cost is not None or self.M > 1 or getattr(self, "_want_states", False)
+        if (self._states is None and self._last is not None and want and not self._needs_generic()
+                and self._model.model_id == N.MODEL_MLP_RELU):
+            # the ReLU model's one kernel does not store states and there is no per-lane form to rerun K1 with
+            # (csrc/mlp_relu.hpp): the model's callables over the command's own bounded actions
+            self._states = self._states_from_callables()
         if self._states is None and self._last is not None and want and not self._needs_generic():
             lib = N.lib()
             p = self._last

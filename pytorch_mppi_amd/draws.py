@@ -119,6 +119,9 @@ class Draws:
             mid = getattr(self._model, "model_id", None)
             rows_only = (self.M > 1 and (mid == N.MODEL_MLP2 or (mid == N.MODEL_MLP and getattr(self._model, "heavy", False)))
                          and not self._needs_generic())
+            # (the ReLU model's one kernel reads its rows from memory at every M and horizon: csrc/rollout_mlp_relu.hip)
+            relu_rows = mid == N.MODEL_MLP_RELU and not self._needs_generic()
+            rows_only = rows_only or relu_rows
             if self.philox_store or rows_only:
                 # generate once, keep the rows for K3 to re-read: Philox + Box-Muller costs more per
                 # element than an HBM read
@@ -128,6 +131,7 @@ class Draws:
                 # row-of-4, however small K is); the generator launch spreads them over the whole chip
                 # and costs one launch (~4 us): it wins from ~16 rows per sample on (tools/k_sweep.py)
                 fill = self.philox_fill if self.philox_fill is not None else rows4 >= 16
+                fill = fill or relu_rows
                 if self.M > 1 and not self._needs_generic():
                     # the multi-rollout K1 reads its rows from memory -- but for the matrix-core MLP kernel of M copies
                     # (csrc/rollout_mlp_split_multi.hip, nu = 4), which generates them on request (philox_fill = False; where
@@ -325,7 +329,8 @@ class Draws:
             return False
         ok = (type(self).__name__ in ("MPPI", "SMPPI") and self.dtype == torch.float32 and self.M == 1
               and self.specific_action_sampler is None and Tn == self.T and not self._needs_generic()
-              and self._model.model_id not in (N.MODEL_MLP, N.MODEL_MLP2))  # the dense MLPs have their own matrix-core K1
+              # the dense MLPs have their own matrix-core K1
+              and self._model.model_id not in (N.MODEL_MLP, N.MODEL_MLP2, N.MODEL_MLP_RELU))
         if not ok:
             return False
         if not self._diagonal_sigma:

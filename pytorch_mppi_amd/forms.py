@@ -174,6 +174,8 @@ class Forms:
         if self.M > 1 and (m.model_id == N.MODEL_MLP2 or (m.model_id == N.MODEL_MLP and getattr(m, "heavy", False))):
             # ... and what _fused_multi_ok reads for this model on top: the weights' range, the horizon, Sigma's form, the switch
             key += (m._param_version, m.hidden, self.T, self._diagonal_sigma, os.environ.get("MPPI_MLP_MULTI"))
+        if m.model_id == N.MODEL_MLP_RELU:
+            key += (m.hidden, self._diagonal_sigma, self.T)      # what _needs_generic_now reads for the ReLU kernel on top
         hit = self._generic_memo
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -193,6 +195,12 @@ class Forms:
         s = self.specific_action_sampler
         if s is not None and type(s).specific_dynamics is not SpecificActionSampler.specific_dynamics:
             return True      # arbitrary Python post-processing of the dynamics (mppi.py:315-317)
+        if self._model.model_id == N.MODEL_MLP_RELU and (not self._diagonal_sigma or self.T * self.nu > 8192):
+            # the ReLU model's one kernel (csrc/rollout_mlp_relu.hip) reads its rows component-wise and has no per-lane form
+            # behind it: a full Sigma runs the callback loop, and so does a horizon whose three action tables (12 T nu bytes)
+            # would not fit the CU's LDS beside the 24 KB of layer-2 planes.  (fp64, other shapes and widths:
+            # mppi_model_supported below; rollout_samples > 1: the model is `heavy`, _fused_multi_ok)
+            return True
         p_ok = N.model_supported(self._model.model_id, self.nx, self.nu, _DT[self.dtype], self._model.hidden)
         return not p_ok
 
@@ -313,6 +321,20 @@ class Forms:
             c = self._terminal_state_cost_fn(visited, applied)               # (K,) or (1,K)
             total = total + (c.squeeze(0) if torch.is_tensor(c) and c.dim() > 1 else c)
         return total, visited, applied
+
+    def _states_from_callables(self):
+        """(1,K,T,nx) visited states of the last fused command through the model's own callables, one batched call per
+        timestep over the bounded actions the command applied -- for a model whose fused kernel stores none and has no
+        per-lane form behind it (M = 1, no process noise: the fused path's conditions)"""
+        v = self.perturbed_action
+        K, T, _ = v.shape
+        x = self.state if tuple(self.state.shape) == (K, self.nx) else self.state.view(1, -1).expand(K, -1)
+        visited = torch.empty(1, K, T, self.nx, device=self.d, dtype=self.dtype)
+        with torch.no_grad():
+            for t in range(T):
+                x = self._dynamics_fn(x, self.u_scale * v[:, t], t)
+                visited[0, :, t] = x[:, :self.nx]
+        return visited
 
     # ------------------------------------------------------------------------------------------
     # lazily materialised public attributes of the fused path (mppi.py:383-385, :411-412)

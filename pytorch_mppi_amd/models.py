@@ -162,6 +162,8 @@ class LinearGoal(NativeModel):
 # (nx, nu) with an instantiation of the split-operand matrix-core kernel (csrc/rollout_mlp_split.hip MPPI_SPLIT_DIMS_*; the
 # last two: its two-output-tile form for 16 < nx <= 32, csrc/rollout_mlp_split32.hip MPPI_SPLIT32_DIMS)
 MLP_MATRIX_CORE_SHAPES = ((16, 4), (8, 2), (12, 6), (16, 8), (32, 8), (24, 6))
+# (nx, nu) with an instantiation of the ReLU kernel (csrc/rollout_mlp_relu.hip MPPI_RELU_DIMS)
+MLP_RELU_SHAPES = ((16, 4), (8, 2), (12, 6), (16, 8))
 
 
 def mlp_kernel_width(nx, nu, hidden):
@@ -201,11 +203,21 @@ class MLPResidual(NativeModel):
     More than 16 states (16 < nx <= 32): `with_process_noise(sd)` and `rollout_samples` 2..4 stay on the matrix cores at the
     (nx, nu) of csrc/rollout_mlp_split32.hip and hidden <= 256 (fp32, a diagonal Sigma, weights within fp16 range): one wave
     per rollout copy, csrc/rollout_mlp_split32_multi.hip, which also stores the visited states.  Everything else at nx > 16
-    and rollout_samples > 1 runs the callback loop (forms._fused_multi_ok)."""
+    and rollout_samples > 1 runs the callback loop (forms._fused_multi_ok).
+
+    `activation="relu"`: x' = x + res_scale * (W2 relu(W1 [x;u] + b1) + b2), the same cost and the same parameter blob under its
+    own model id (`MPPI_MODEL_MLP_RELU`, csrc/mlp_relu.hpp).  Its one fused form is the matrix-core kernel
+    csrc/rollout_mlp_relu.hip -- fp32, the (nx, nu) of `MLP_RELU_SHAPES`, hidden <= 256 (zero-padded: relu(0) = 0), one rollout
+    per sequence, a diagonal Sigma -- which runs both layers on three-piece bf16 operands and so has no weight-range limit
+    (`flags()` is 0).  fp64, rollout_samples > 1, process noise, a full Sigma, the visited states and every other shape run the
+    callback loop on these callables (forms._needs_generic_now)."""
     model_id = N.MODEL_MLP
 
-    def __init__(self, W1, b1, W2, b2, nx, nu, res_scale=0.1, q_state=None, q_control=None):
+    def __init__(self, W1, b1, W2, b2, nx, nu, res_scale=0.1, q_state=None, q_control=None, activation="tanh"):
         super().__init__()
+        if activation not in ("tanh", "relu"):
+            raise ValueError(f"activation must be 'tanh' or 'relu', not {activation!r}")
+        self.activation = activation
         self.W1, self.b1, self.W2, self.b2 = (torch.as_tensor(t) for t in (W1, b1, W2, b2))
         self.nx, self.nu = int(nx), int(nu)
         # `hidden` is what the kernels see: odd widths are zero-padded to the next width the matrix-core kernels are
@@ -216,6 +228,13 @@ class MLPResidual(NativeModel):
         # multi-rollout form spills registers, csrc/rollout_mlp.hip) -- at rollout_samples > 1 only what the matrix-core kernel
         # of M copies promises statically leaves the callback loop (forms._fused_multi_ok)
         self.heavy = self.nx > 16
+        if activation == "relu":
+            # one kernel, no per-lane form: where it has no instantiation the width stays the model's own and the engine's static
+            # answer (mppi_model_supported) keeps the model on the callback loop; rollout_samples > 1 always does (`heavy`)
+            self.model_id = N.MODEL_MLP_RELU
+            self.heavy = True
+            if (self.nx, self.nu) not in MLP_RELU_SHAPES:
+                self.hidden = self.hidden_units
         self.res_scale = float(res_scale)
         self.q_state = torch.ones(self.nx, dtype=torch.float64) if q_state is None else torch.as_tensor(q_state,
                 dtype=torch.float64).reshape(-1)
@@ -230,14 +249,17 @@ class MLPResidual(NativeModel):
         weights (-2 W2) must stay inside fp16's range.  Weights beyond it -- checked here every time the parameter
         version changes, i.e. also after `invalidate()` behind an in-place update -- select the exact fp32 MFMA kernel,
         which has no such
-        limit."""
+        limit.  The ReLU kernel (csrc/rollout_mlp_relu.hip) runs both layers on three-piece bf16 operands, which keep fp32's
+        exponent range: no limit, no flag."""
+        if self.activation == "relu":
+            return 0
         if getattr(self, "_flags_version", None) != self._param_version:
             self._flags = N.MODEL_FLAG_EXACT_FP32 if float(torch.as_tensor(self.W2).abs().max()) >= 3.0e4 else 0
             self._flags_version = self._param_version
         return self._flags
 
     @classmethod
-    def random(cls, nx, nu, hidden, seed=2, dtype=torch.float32, res_scale=0.1):
+    def random(cls, nx, nu, hidden, seed=2, dtype=torch.float32, res_scale=0.1, activation="tanh"):
         """torch.nn.Linear default initialisation under a private generator state."""
         g = torch.random.get_rng_state()
         torch.manual_seed(seed)
@@ -247,7 +269,7 @@ class MLPResidual(NativeModel):
         with torch.no_grad():
             return cls(l1.weight.detach().to(dtype).clone(), l1.bias.detach().to(dtype).clone(),
                        l2.weight.detach().to(dtype).clone(), l2.bias.detach().to(dtype).clone(),
-                       nx, nu, res_scale)
+                       nx, nu, res_scale, activation=activation)
 
     def _param_list(self):
         W1, b1, W2 = (self.W1, self.b1, self.W2) if self.hidden == self.hidden_units else pad_hidden(self.W1, self.b1,
@@ -256,7 +278,8 @@ class MLPResidual(NativeModel):
 
     def dynamics(self, state, action, t=None):
         W1, b1, W2, b2 = (t.to(state.device, state.dtype) for t in (self.W1, self.b1, self.W2, self.b2))
-        h = torch.tanh(torch.cat((state, action), dim=1) @ W1.T + b1)
+        h = torch.cat((state, action), dim=1) @ W1.T + b1
+        h = torch.relu(h) if self.activation == "relu" else torch.tanh(h)
         return self._noisy(state + self.res_scale * (h @ W2.T + b2))
 
     def running_cost(self, state, action, t=None):
