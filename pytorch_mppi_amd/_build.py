@@ -19,7 +19,7 @@ OBJ_DIR = os.path.join(CSRC, "build" + SUFFIX)
 SOURCES = ["capi.hip", "dist.hip", "group.hip", "update.hip", "rollout_pendulum.hip", "rollout_integrator.hip",
            "rollout_linear_goal.hip", "rollout_mlp.hip", "rollout_mlp_mfma.hip", "rollout_mlp_split.hip",
                    "rollout_mlp_split32.hip", "rollout_mlp_split_multi.hip", "rollout_mlp_deep.hip", "rollout_mlp2.hip",
-           "rollout_mlp_deep_multi.hip", "rollout_mlp_split32_multi.hip", "rollout_mlp_relu.hip",
+           "rollout_mlp_deep_multi.hip", "rollout_mlp_split32_multi.hip", "rollout_mlp_relu.hip", "rollout_mlp_deep_relu.hip",
            "noise_torch.hip"]
 # translation units: (source, object name, extra flags).  The two heaviest sources are compiled as several units each
 # (groups of model dimensions selected with a define) so that the parallel build is not one long compile
@@ -55,7 +55,7 @@ def _units():
             "rollout_mlp_split_multi_g0.o": 60, "rollout_mlp_split_multi_g1.o": 60,
             "rollout_mlp_deep_multi_g0.o": 40, "rollout_mlp_deep_multi_g1.o": 40, "rollout_mlp_deep_multi_g2.o": 40,
             "rollout_mlp_split32_multi_g0.o": 25, "rollout_mlp_split32_multi_g1.o": 25,
-            "rollout_mlp_relu.o": 60, "rollout_mlp_deep.o": 40, "rollout_mlp2_g0.o": 60, "rollout_mlp2_g1.o": 60, "rollout_mlp2_g2.o": 40}
+            "rollout_mlp_relu.o": 60, "rollout_mlp_deep_relu.o": 70, "rollout_mlp_deep.o": 40, "rollout_mlp2_g0.o": 60, "rollout_mlp2_g1.o": 60, "rollout_mlp2_g2.o": 40}
     return sorted(units, key=lambda u: -cost.get(u[1], 5))
 # -ffp-contract=fast: mul+add pairs fuse into v_fma / v_pk_fma.  torch eager rounds twice where
 # the kernels round once, a <= 1 ulp difference per operation that the parity tests bound
@@ -85,6 +85,8 @@ EXTRA = {"update.hip": ["-mllvm", "-pragma-unroll-threshold=200000"],
          # the ReLU kernel: every layer-1 accumulator is read by the VALU (max, split), so MFMA results go straight into
          # VGPRs; no packed fp32 arithmetic in the split
          "rollout_mlp_relu.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] + NO_PK_F32,
+         # its two-hidden-layer form: the same arithmetic, the same flags
+         "rollout_mlp_deep_relu.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] + NO_PK_F32,
          # the KMPPI-fused K1 (rollout_kmppi.hpp) pins 256 control points in the AGPRs and reads its 4 x nu
          # accumulator tile with the VALU: same flag for every unit that instantiates it (jit.py passes it too)
          "rollout_integrator.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

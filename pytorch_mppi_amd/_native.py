@@ -21,6 +21,7 @@ E_GROUP_PEER = -5
 MODEL_NONE, MODEL_PENDULUM, MODEL_INTEGRATOR, MODEL_LINEAR_GOAL, MODEL_MLP = 0, 1, 2, 3, 4
 MODEL_MLP2 = 5             # two hidden layers (csrc/mlp_deep.hpp; in include/mppi_amd.h from the next ABI bump)
 MODEL_MLP_RELU = 6         # one hidden layer of ReLU units (csrc/mlp_relu.hpp; in include/mppi_amd.h from the next ABI bump)
+MODEL_MLP2_RELU = 7        # two hidden layers of ReLU units (csrc/mlp_deep_relu.hpp; in include/mppi_amd.h from the next ABI bump)
 MODEL_CUSTOM_BASE = 100
 MODEL_FLAG_EXACT_FP32 = 1
 MODEL_FLAG_NO_WIDE = 2
@@ -133,6 +134,7 @@ EXTRA_SYMBOLS = {
     "mppi_stat_mlp_deep_launches": (C.c_int64, []),        # (csrc/mlp_deep.hpp)
     "mppi_stat_mlp_split_multi_launches": (C.c_int64, []),  # (csrc/mlp_split_multi.hpp)
     "mppi_stat_mlp_relu_launches": (C.c_int64, []),         # (csrc/mlp_relu.hpp)
+    "mppi_stat_mlp_deep_relu_launches": (C.c_int64, []),    # (csrc/mlp_deep_relu.hpp)
     # (csrc/mlp_deep_multi.hpp: the two-hidden-layer model at rollout_samples 2..4 -- the launcher's static promise, its launches)
     "mppi_mlp_deep_multi_supported": (C.c_int, [C.c_int32] * 6),
     "mppi_stat_mlp_deep_multi_launches": (C.c_int64, []),

@@ -632,9 +632,9 @@ class MPPI(Draws, Forms, JitGlue):
         stores them (:349-350, :366)."""
         want = self.terminal_state_cost is not None or self.M > 1 or getattr(self, "_want_states", False)
         if (self._states is None and self._last is not None and want and not self._needs_generic()
-                and self._model.model_id == N.MODEL_MLP_RELU):
-            # the ReLU model's one kernel does not store states and there is no per-lane form to rerun K1 with
-            # (csrc/mlp_relu.hpp): the model's callables over the command's own bounded actions
+                and self._model.model_id in (N.MODEL_MLP_RELU, N.MODEL_MLP2_RELU)):
+            # a ReLU model's one kernel does not store states and there is no per-lane form to rerun K1 with
+            # (csrc/mlp_relu.hpp, csrc/mlp_deep_relu.hpp): the model's callables over the command's own bounded actions
             self._states = self._states_from_callables()
         if self._states is None and self._last is not None and want and not self._needs_generic():
             lib = N.lib()

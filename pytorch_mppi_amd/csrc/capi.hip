@@ -11,6 +11,7 @@
 #include "dispatch.hpp"
 #include "mlp_deep.hpp"      // MPPI_MODEL_MLP2, its blob and mppi_stat_mlp_deep_launches (rollout_mlp_deep.hip, rollout_mlp2.hip)
 #include "mlp_relu.hpp"      // MPPI_MODEL_MLP_RELU and mppi_stat_mlp_relu_launches (rollout_mlp_relu.hip)
+#include "mlp_deep_relu.hpp" // MPPI_MODEL_MLP2_RELU and mppi_stat_mlp_deep_relu_launches (rollout_mlp_deep_relu.hip)
 #include "mlp_split32.hpp"   // mppi_stat_mlp_split32_launches: defined by rollout_mlp_split32.hip, part of this C-ABI
 #include "mlp_split_multi.hpp"   // mppi_stat_mlp_split_multi_launches: defined by rollout_mlp_split_multi.hip, part of this C-ABI
 #include "update.hpp"
@@ -231,6 +232,8 @@ int make_args(const MppiProblem* p, KArgs<T>& a) {
     if (p->model_id == MPPI_MODEL_MLP2) need = mlp2_blob_elems(p->nx, p->nu, p->hidden);
     // one hidden layer of ReLU units: MPPI_MODEL_MLP's layout (csrc/mlp_relu.hpp)
     if (p->model_id == MPPI_MODEL_MLP_RELU) need = mlp_relu_blob_elems(p->nx, p->nu, p->hidden);
+    // two hidden layers of ReLU units: MPPI_MODEL_MLP2's layout (csrc/mlp_deep_relu.hpp)
+    if (p->model_id == MPPI_MODEL_MLP2_RELU) need = mlp2_blob_elems(p->nx, p->nu, p->hidden);
     if (need > 0 && p->model_params != nullptr && p->model_params_elems < need) {
       char msg[200];
       snprintf(msg, sizeof(msg), "model_params holds %d elements (model_params_elems), this model's blob needs %lld (layout: include/mppi_amd.h)",
@@ -335,6 +338,10 @@ int do_rollout(const MppiProblem* p, hipStream_t st, int fuse = -1, bool kmppi =
       if constexpr (sizeof(T) == 4) r = rollout_mlp_relu(a, st);
       else r = MPPI_E_UNSUPPORTED;
       break;
+    case MPPI_MODEL_MLP2_RELU:     // likewise (csrc/mlp_deep_relu.hpp)
+      if constexpr (sizeof(T) == 4) r = rollout_mlp_deep_relu(a, st);
+      else r = MPPI_E_UNSUPPORTED;
+      break;
     default: {
       const int slot = p->model_id - MPPI_MODEL_CUSTOM_BASE;
       if (slot < 0 || slot >= MAX_CUSTOM) return fail(MPPI_E_UNSUPPORTED, "mppi_rollout_cost: model has no fused kernel");
@@ -374,6 +381,7 @@ extern "C" int mppi_model_supported(int32_t model_id, int32_t nx, int32_t nu, in
     case MPPI_MODEL_MLP: return supported_mlp(nx, nu, hidden);
     case MPPI_MODEL_MLP2: return supported_mlp2(nx, nu, hidden);
     case MPPI_MODEL_MLP_RELU: return dtype == MPPI_F32 && supported_mlp_relu(nx, nu, hidden);
+    case MPPI_MODEL_MLP2_RELU: return dtype == MPPI_F32 && supported_mlp2_relu(nx, nu, hidden);
     default: {
       const int slot = model_id - MPPI_MODEL_CUSTOM_BASE;
       if (slot < 0 || slot >= MAX_CUSTOM) return 0;

@@ -119,8 +119,9 @@ class Draws:
             mid = getattr(self._model, "model_id", None)
             rows_only = (self.M > 1 and (mid == N.MODEL_MLP2 or (mid == N.MODEL_MLP and getattr(self._model, "heavy", False)))
                          and not self._needs_generic())
-            # (the ReLU model's one kernel reads its rows from memory at every M and horizon: csrc/rollout_mlp_relu.hip)
-            relu_rows = mid == N.MODEL_MLP_RELU and not self._needs_generic()
+            # (the ReLU models' one kernel each reads its rows from memory at every M and horizon: csrc/rollout_mlp_relu.hip,
+            # csrc/rollout_mlp_deep_relu.hip)
+            relu_rows = mid in (N.MODEL_MLP_RELU, N.MODEL_MLP2_RELU) and not self._needs_generic()
             rows_only = rows_only or relu_rows
             if self.philox_store or rows_only:
                 # generate once, keep the rows for K3 to re-read: Philox + Box-Muller costs more per
@@ -330,7 +331,7 @@ class Draws:
         ok = (type(self).__name__ in ("MPPI", "SMPPI") and self.dtype == torch.float32 and self.M == 1
               and self.specific_action_sampler is None and Tn == self.T and not self._needs_generic()
               # the dense MLPs have their own matrix-core K1
-              and self._model.model_id not in (N.MODEL_MLP, N.MODEL_MLP2, N.MODEL_MLP_RELU))
+              and self._model.model_id not in (N.MODEL_MLP, N.MODEL_MLP2, N.MODEL_MLP_RELU, N.MODEL_MLP2_RELU))
         if not ok:
             return False
         if not self._diagonal_sigma:

@@ -174,8 +174,8 @@ class Forms:
         if self.M > 1 and (m.model_id == N.MODEL_MLP2 or (m.model_id == N.MODEL_MLP and getattr(m, "heavy", False))):
             # ... and what _fused_multi_ok reads for this model on top: the weights' range, the horizon, Sigma's form, the switch
             key += (m._param_version, m.hidden, self.T, self._diagonal_sigma, os.environ.get("MPPI_MLP_MULTI"))
-        if m.model_id == N.MODEL_MLP_RELU:
-            key += (m.hidden, self._diagonal_sigma, self.T)      # what _needs_generic_now reads for the ReLU kernel on top
+        if m.model_id in (N.MODEL_MLP_RELU, N.MODEL_MLP2_RELU):
+            key += (m.hidden, self._diagonal_sigma, self.T)      # what _needs_generic_now reads for the ReLU kernels on top
         hit = self._generic_memo
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -200,6 +200,10 @@ class Forms:
             # behind it: a full Sigma runs the callback loop, and so does a horizon whose three action tables (12 T nu bytes)
             # would not fit the CU's LDS beside the 24 KB of layer-2 planes.  (fp64, other shapes and widths:
             # mppi_model_supported below; rollout_samples > 1: the model is `heavy`, _fused_multi_ok)
+            return True
+        if self._model.model_id == N.MODEL_MLP2_RELU and (not self._diagonal_sigma or self.T * self.nu > 5376):
+            # likewise the two-hidden-layer ReLU model (csrc/rollout_mlp_deep_relu.hip): its hidden->hidden planes take 96 KB of
+            # the CU's 160 KB of LDS at H = 128 (+ 512 bytes of bias), which leaves 63 KB for the action tables
             return True
         p_ok = N.model_supported(self._model.model_id, self.nx, self.nu, _DT[self.dtype], self._model.hidden)
         return not p_ok

@@ -301,21 +301,37 @@ class MLPResidual2(NativeModel):
 
     `with_process_noise(sd)` and `rollout_samples` 2..4 stay on the matrix cores at those shapes and widths (fp32, a diagonal
     Sigma, weights within fp16 range): one wave per rollout copy, csrc/rollout_mlp_deep_multi.hip.  Everything else at
-    rollout_samples > 1 runs the callback loop (forms._fused_multi_ok)."""
+    rollout_samples > 1 runs the callback loop (forms._fused_multi_ok).
+
+    `activation="relu"`: x' = x + res_scale * (W3 relu(W2 relu(W1 [x;u] + b1) + b2) + b3), the same cost and the same parameter
+    blob under its own model id (`MPPI_MODEL_MLP2_RELU`, csrc/mlp_deep_relu.hpp).  Its one fused form is the matrix-core kernel
+    csrc/rollout_mlp_deep_relu.hip -- fp32, the (nx, nu) of `MLP2_MATRIX_CORE_SHAPES`, both hidden layers <= 128 units
+    (zero-padded to 64 or 128: relu(0) = 0), one rollout per sequence, a diagonal Sigma -- which runs all three layers on
+    three-piece bf16 operands and so has no weight-range limit (`flags()` is 0).  fp64, rollout_samples > 1, process noise, a
+    full Sigma, the visited states and every other shape run the callback loop on these callables (forms._needs_generic_now)."""
     model_id = N.MODEL_MLP2
     # the per-lane kernels keep one rolled copy of the step and serve one state rollout per action sequence (their multi-rollout
     # form spills registers, csrc/rollout_mlp2.hip): at rollout_samples > 1 there is no per-lane form to fall back on, and only
     # what the matrix-core kernel of M copies promises statically leaves the callback loop (forms._fused_multi_ok)
     heavy = True
 
-    def __init__(self, W1, b1, W2, b2, W3, b3, nx, nu, res_scale=0.1, q_state=None, q_control=None):
+    def __init__(self, W1, b1, W2, b2, W3, b3, nx, nu, res_scale=0.1, q_state=None, q_control=None, activation="tanh"):
         super().__init__()
+        if activation not in ("tanh", "relu"):
+            raise ValueError(f"activation must be 'tanh' or 'relu', not {activation!r}")
+        self.activation = activation
         self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = (torch.as_tensor(t) for t in (W1, b1, W2, b2, W3, b3))
         self.nx, self.nu = int(nx), int(nu)
         self.hidden_units = (int(self.W1.shape[0]), int(self.W2.shape[0]))
         widest = max(self.hidden_units)
         fits = [w for w in (32, 64, 128) if widest <= w] if (self.nx, self.nu) in MLP2_MATRIX_CORE_SHAPES else []
         self.hidden = fits[0] if fits else -(-widest // 32) * 32
+        if activation == "relu":
+            # one kernel (widths 64 and 128), no per-lane form: where it has no instantiation the width stays the model's own and
+            # the engine's static answer (mppi_model_supported) keeps the model on the callback loop; rollout_samples > 1 always
+            # does (`heavy`, forms._fused_multi_ok)
+            self.model_id = N.MODEL_MLP2_RELU
+            self.hidden = max(fits[0], 64) if fits else widest
         self.res_scale = float(res_scale)
         self.q_state = torch.ones(self.nx, dtype=torch.float64) if q_state is None else torch.as_tensor(q_state,
                 dtype=torch.float64).reshape(-1)
@@ -330,7 +346,10 @@ class MLPResidual2(NativeModel):
     def flags(self):
         """The matrix-core kernel runs both 16-bit layers on two-piece fp16 operands: the folded weights -2 (2 log2 e) W2 and
         -2 W3 must stay inside fp16's range.  Weights beyond it -- checked every time the parameter version changes -- select
-        the per-lane kernel, which has no such limit."""
+        the per-lane kernel, which has no such limit.  The ReLU kernel (csrc/rollout_mlp_deep_relu.hip) runs every layer on
+        three-piece bf16 operands, which keep fp32's exponent range: no limit, no flag."""
+        if self.activation == "relu":
+            return 0
         if getattr(self, "_flags_version", None) != self._param_version:
             folded = max(4.0 * math.log2(math.e) * float(self.W2.abs().max()), 2.0 * float(self.W3.abs().max()))
             self._flags = N.MODEL_FLAG_EXACT_FP32 if folded >= 6.0e4 else 0
@@ -338,7 +357,7 @@ class MLPResidual2(NativeModel):
         return self._flags
 
     @classmethod
-    def random(cls, nx, nu, hidden1, hidden2, seed=2, dtype=torch.float32, res_scale=0.1):
+    def random(cls, nx, nu, hidden1, hidden2, seed=2, dtype=torch.float32, res_scale=0.1, activation="tanh"):
         """torch.nn.Linear default initialisation under a private generator state."""
         g = torch.random.get_rng_state()
         torch.manual_seed(seed)
@@ -346,7 +365,7 @@ class MLPResidual2(NativeModel):
         torch.random.set_rng_state(g)
         with torch.no_grad():
             wb = [t.detach().to(dtype).clone() for l in ls for t in (l.weight, l.bias)]
-        return cls(*wb, nx, nu, res_scale)
+        return cls(*wb, nx, nu, res_scale, activation=activation)
 
     def _param_list(self):
         """csrc/mlp_deep.hpp: W1 (H,nx+nu) | b1 (H) | W2T (H,H) | b2 (H) | W3T (H,nx) | b3 (nx) | s | qx | qu"""
@@ -361,7 +380,8 @@ class MLPResidual2(NativeModel):
     def dynamics(self, state, action, t=None):
         W1, b1, W2, b2, W3, b3 = (t.to(state.device, state.dtype) for t in (self.W1, self.b1, self.W2, self.b2, self.W3,
                 self.b3))
-        h = torch.tanh(torch.tanh(torch.cat((state, action), dim=1) @ W1.T + b1) @ W2.T + b2)
+        f = torch.relu if self.activation == "relu" else torch.tanh
+        h = f(f(torch.cat((state, action), dim=1) @ W1.T + b1) @ W2.T + b2)
         return self._noisy(state + self.res_scale * (h @ W3.T + b3))
 
     running_cost = MLPResidual.running_cost
